@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: KITTI 256x832 stereo-sequence training samples/sec (forward + backward + Adam) on synthetic data.
 
-    python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}]
+    python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -17,7 +17,10 @@ launcher, `--gpus N` (N > 1) spawns the N rank processes itself before any GPU c
 `value` counts samples of all ranks over the slowest rank's time; `roofline*` objects come from HIP-event brackets around
 every kernel call of one serialised step measured live (`roofline` = the calls whose plan ran conv_pipe_kernel, attributed
 through the library's plan log; `conv_calls_by_kernel` lists every kernel family); `host_enqueue_ms` is the host time to
-enqueue one step; `cpu_baseline` is the CPU oracle timed on this host."""
+enqueue one step; `cpu_baseline` is the CPU oracle timed on this host.  `ms_per_step` is the wall time of one of the K
+timed steps.  Inputs and initial weights are seeded, so the same arguments give the same inputs in every run;
+`--dump-outputs DIR` writes the loss terms, weight gradients and updated weights of one more step from that seeded
+state, through the eager step on the timed loop's streams, there after the timed steps (see dump_outputs)."""
 import argparse
 import json
 import os
@@ -148,14 +151,50 @@ def build(args, cfg, device, world, rank):
         opt.zero_grad()
         loss.backward()
         opt.join_wgrad()                # weight-gradient stream joins the main stream
-        return (terms["total"],)
+        return terms["total"], terms    # detached loss terms
 
     def step():
         out = fwd_bwd()
         opt.step()                      # (gradient all-reduce +) fused Adam
         return out
 
-    return step, fwd_bwd, opt, ddp
+    named_nets = {"pose": pose_net, "disp": disp_net}
+    if feat_net is not None:
+        named_nets["feat"] = feat_net
+    return step, fwd_bwd, opt, ddp, named_nets
+
+
+DUMP_SAMPLE = 1 << 18                   # elements kept of a larger tensor by --dump-outputs (<= 51 MB in all)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, terms, nets):
+    """--dump-outputs: what one training step computed -- every loss term, and of every network parameter its weight
+    gradient and its value after the Adam update -- as <path>/<name>.npy in float32.  A tensor of more than DUMP_SAMPLE
+    elements is represented by DUMP_SAMPLE of them, at sorted indices drawn from a fixed seed (flattened, the same for
+    the value and the gradient), so that two builds compare element for element and every config stays under 64 MB.
+    main() runs that step after the timed steps, from the seeded initial state, as the eager step on the timed loop's streams
+    with ordered weight-gradient and bias reductions (dvf.conv.set_deterministic): its inputs are
+    the same in every run and so are these arrays.  The last timed step's own arrays are not written: they start from
+    weights that the float-atomic rounding of all earlier steps has moved differently in every run."""
+    import numpy as np
+    import torch
+    arrays = {"loss_" + k: v.detach().float().cpu().numpy() for k, v in terms.items()}
+    for net_name, net in nets.items():
+        for k, p in net.named_parameters():
+            idx = None
+            if p.numel() > DUMP_SAMPLE:
+                g = torch.Generator().manual_seed(0)
+                idx = torch.randperm(p.numel(), generator=g)[:DUMP_SAMPLE].sort().values.to(p.device)
+            for kind, v in (("param", p.detach()), ("grad", p._dvf_grad)):    # _dvf_grad: its slice of the gradient arena
+                arrays[f"{kind}_{net_name}.{k}"] = (v if idx is None else v.reshape(-1)[idx]).float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return len(arrays), total
 
 
 def pmc_traffic(kernel):
@@ -299,7 +338,14 @@ def main():
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--serialize", action="store_true",
                     help="no side streams (weight gradients, pose network) -- for per-kernel profiles; not the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after an eager timed loop, run one more eager step from the seeded initial state on the timed loop's "
+                         "streams, with ordered gradient reductions, and write its loss terms, weight gradients and "
+                         "updated weights (a fixed sample of the large ones) to DIR/<name>.npy, to compare two builds "
+                         "output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     cfg = CONFIGS[args.config]
     for k in ("batch", "height", "width"):
         if getattr(args, k) is None:
@@ -339,7 +385,9 @@ def main():
         args.no_graph = not args.graph_ddp
     elif not args.graph:
         args.no_graph = True
-    step, fwd_bwd, opt, ddp = build(args, cfg, device, world, rank)
+    step, fwd_bwd, opt, ddp, nets = build(args, cfg, device, world, rank)
+    if args.dump_outputs:                 # the seeded state the --dump-outputs step starts from
+        initial_params, initial_opt = opt.flat_p.clone(), opt.state_dict()
     use_graph = not args.no_graph
     from dvf.engine import GraphedStep
     if auto:
@@ -380,6 +428,10 @@ def main():
                 return out
     else:
         run = step
+    if args.dump_outputs and use_graph:
+        # the seeded step does not repeat after a graph-timed loop (its gradients differ from run to run and from the
+        # eager step's): no dump rather than a wrong one
+        sys.exit("bench.py: --dump-outputs needs an eager timed loop (--no-graph, or the default launch mode picking eager)")
     log("warm-up")
     for _ in range(args.warmup):
         out = run()
@@ -405,6 +457,27 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     loss = float(out[0])
+    if args.dump_outputs:
+        # One more step, from the seeded initial state, through the eager step on the timed loop's streams (side streams,
+        # early per-bucket Adam on the update stream).  After the timed steps the weights depend on how each step's
+        # float-atomic weight-gradient and bias sums happened to round, and Adam carries that into them, so the last timed
+        # step's arrays differ from run to run by up to their whole range.  This step differs from an eager timed one only
+        # in using the library's ordered reductions for those sums, so that it writes the same arrays in every run.  Every
+        # rank runs it (it holds the gradient exchange).
+        from dvf import conv as _C
+        from dvf import lib as _L
+        _C.set_deterministic(True)
+        try:
+            opt.flat_p.copy_(initial_params)
+            opt.load_state_dict(initial_opt)
+            _L.PACK_EPOCH += 1                                 # packed weight copies are rebuilt from the restored weights
+            dumped = step()
+            fence()
+        finally:
+            _C.set_deterministic(False)
+        if rank == 0:
+            n, nbytes = dump_outputs(args.dump_outputs, dumped[1], nets)
+            log("dumped %d arrays (%.1f MB) to %s" % (n, nbytes / 2**20, args.dump_outputs))
 
     # the data-parallel exchange on its own: the gradient arena all-reduced in the step's buckets, nothing overlapping it
     allreduce_ms = None

@@ -256,7 +256,7 @@ def test_other_bench_configs_geometries_and_plans(config):
     cfg = bench.CONFIGS[config]
     args = argparse.Namespace(batch=cfg["batch"], height=cfg["height"], width=cfg["width"], seed=0, force_ddp=False,
                               no_graph=True)
-    step, fwd_bwd, opt, _ = bench.build(args, cfg, torch.device(DEV), 1, 0)
+    step, fwd_bwd, opt, _, nets = bench.build(args, cfg, torch.device(DEV), 1, 0)
     fwd_bwd()                                         # (first pass: packs, workspaces)
     C.GEOM_LOG, L.PLAN_LOG = [], set()
     try:
@@ -268,7 +268,7 @@ def test_other_bench_configs_geometries_and_plans(config):
         C.GEOM_LOG, L.PLAN_LOG = None, None
     assert torch.isfinite(total).all(), float(total)
     assert float(opt.flat_g.abs().max()) > 0 and torch.isfinite(opt.flat_g).all()
-    del step, fwd_bwd, opt
+    del step, fwd_bwd, opt, nets
     torch.cuda.empty_cache()
     assert geoms and step_plans
     _check_geometries(geoms, 10000 * config)

@@ -2,6 +2,8 @@
 concat, crop_like, parity-class transposed convolution, split-K) and of the small memory-bound ops, against
 torch CPU fp32 (the arithmetic the reference's nn.Conv2d / nn.ConvTranspose2d / F.interpolate run on).
 Bound: 1e-4 relative (max-abs error / max-abs reference)."""
+import zlib
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -64,7 +66,7 @@ CASES = [
 def test_conv_fwd_bwd(case):
     from dvf.conv import ConvFn
     name, segs, cout, k, stride, pad, opad, transposed, act, (n, h, w), out_hw = case
-    gen = torch.Generator().manual_seed(hash(name) % 10000)
+    gen = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 10000)
     cin = sum(segs)
     xs = [torch.randn(n, c, h, w, generator=gen) for c in segs]
     wshape = (cin, cout, k, k) if transposed else (cout, cin, k, k)

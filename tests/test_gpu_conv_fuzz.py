@@ -3,6 +3,7 @@ sizes 1..7, strides 1/2, Conv2d and ConvTranspose2d, 1..3 input segments, odd si
 both sides of the 16 / 32 / 64-row tile boundaries, with and without the fused bias column -- against torch CPU.
 Bound: 1e-4 relative (max-abs error / max-abs reference), fp32."""
 import random
+import zlib
 
 import pytest
 import torch
@@ -46,7 +47,7 @@ def test_wgrad_envelope(case):
     from dvf.conv import ConvFn, ReluTag
     from dvf import lib as L
     name, segs, cout, k, stride, pad, opad, transposed, (n, h, w), fused = case
-    gen = torch.Generator().manual_seed(hash(name) % 100000)
+    gen = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 100000)
     cin = sum(segs)
     xs = [torch.randn(n, c, h, w, generator=gen) for c in segs]
     wshape = (cin, cout, k, k) if transposed else (cout, cin, k, k)
@@ -80,7 +81,7 @@ def test_fwd_dgrad_envelope(case):
     from dvf.conv import ConvFn, ReluTag
     from dvf import lib as L
     name, segs, cout, k, stride, pad, opad, transposed, (n, h, w), fused = case
-    gen = torch.Generator().manual_seed(hash(name) % 100000 + 7)
+    gen = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 100000 + 7)
     cin = sum(segs)
     xs = [torch.randn(n, c, h, w, generator=gen) for c in segs]
     if fused:

@@ -5,7 +5,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "depth-vo-feat_amd")]
 import torch, bench
 from torch.profiler import profile, ProfilerActivity
 args = argparse.Namespace(batch=4, height=256, width=832, seed=0, no_graph=True, force_ddp=False, graph_ddp=False)
-step, fwd_bwd, opt, ddp = bench.build(args, bench.CONFIGS[2], torch.device("cuda", 0), 1, 0)
+step, fwd_bwd, opt, ddp, nets = bench.build(args, bench.CONFIGS[2], torch.device("cuda", 0), 1, 0)
 for _ in range(3): step()
 torch.cuda.synchronize()
 with profile(activities=[ProfilerActivity.CPU], record_shapes=True, with_stack=True) as prof:
