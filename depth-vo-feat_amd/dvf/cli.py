@@ -26,7 +26,10 @@ def add_common_flags(parser):
     g.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay")
     g.add_argument("--deterministic", action="store_true",
                    help="weight / bias gradients summed in a fixed order (no float atomics): runs from identical state are "
-                        "bit-identical, as on the reference's CPU path; costs ~5 %% of a step")
+                        "bit-identical, as on the reference's CPU path, except the gradients of the FeatExtractor's "
+                        "parameters when the feature term is on (the photometric backward scatters the source-feature "
+                        "gradients, and the depthwise up-convolutions sum their weight gradients, with float atomics); "
+                        "costs ~5 %% of a step")
     g.add_argument("--reference-stereo-pose", action="store_true",
                    help="feed the dataset's T_R2L file vector (0,0,0,Tx,0,0) unchanged into pose_vec2mat / the stereo-pose "
                         "MSE target, exactly as the reference does (unsupervise.py:101, train.py:201); default: convert it "

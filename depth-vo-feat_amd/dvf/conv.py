@@ -34,18 +34,25 @@ def conv_out_size(h, k, stride, pad, opad, transposed):
 _WS = {}      # (device, stream) -> split-K scratch shared by the convolutions of that stream
 
 
-def _workspace(nfloats, device, raw_stream=None):
-    """Scratch for split-K partial tiles: one buffer per compute stream (kernels of one stream are ordered, so they can
-    share it); it only grows.  During a HIP-graph capture the current stream is the capture's own, so there is no
-    cached buffer for it: the scratch then comes from the capture's private memory pool (one allocation per call, at
-    capture time only) -- the captured step must run the same split-K reduction as the eager one, not the float-atomic
-    fallback of a missing workspace."""
+def _workspace(nfloats, device, raw_stream=None, stream=None):
+    """Scratch for split-K partial tiles: one buffer per stream (kernels of one stream are ordered, so they can share
+    it); it only grows.  ``stream``: the torch stream the kernels run on when that is not the current stream (the
+    weight-gradient side stream, ``raw_stream`` its handle).  The buffer is allocated under that stream, so that torch's
+    caching allocator gives the block of a buffer replaced by a larger one only to later allocations of the same stream,
+    which run after every kernel that used it: allocated under the compute stream, the block would be free for the next
+    compute-stream tensor while side-stream kernels not yet joined still write their slabs into it.
+    During a HIP-graph capture no cached (eager) buffer is returned: the scratch comes from the capture's private memory
+    pool (one allocation per call, at capture time only) -- the captured step must run the same ordered reduction as the
+    eager one, not the float-atomic fallback of a missing workspace, and an eager growth must not free memory that the
+    graph still uses."""
+    capturing = torch.cuda.is_current_stream_capturing()
     key = (device, L.stream_raw() if raw_stream is None else raw_stream)
-    buf = _WS.get(key)
+    buf = None if capturing else _WS.get(key)
     if buf is None or buf.numel() < nfloats:
-        if torch.cuda.is_current_stream_capturing():
-            return torch.empty(max(int(nfloats), 1), device=device, dtype=torch.float32)
-        _WS[key] = buf = torch.empty(max(int(nfloats), 1 << 20), device=device, dtype=torch.float32)
+        with (torch.cuda.stream(stream) if stream is not None else _NULL):
+            if capturing:
+                return torch.empty(max(int(nfloats), 1), device=device, dtype=torch.float32)
+            _WS[key] = buf = torch.empty(max(int(nfloats), 1 << 20), device=device, dtype=torch.float32)
     return buf
 
 
@@ -376,7 +383,7 @@ class ConvFn(torch.autograd.Function):
                 with (L.timed("conv_wgrad", 2 * g.macs, tag=g.tag) if timing else _NULL):
                     # (DETERMINISTIC: partial tiles through a per-stream scratch, summed in fixed order; else float atomics)
                     wsf = _wgrad_ws_floats(ctx.wparam if arena else weight, desc, segc) if DETERMINISTIC else 0
-                    wws = _workspace(wsf, dpre.device, wst) if wsf > 0 else None
+                    wws = _workspace(wsf, dpre.device, wst, side) if wsf > 0 else None
                     rc = lib.dvf_conv2d_wgrad_det(g.dref, ctx.inarr, g.segarr, g.nseg, dprep, dw.data_ptr(), 1 if arena else 0,
                                                   dbias.data_ptr() if (fused_out and need_b) else None, 1 if acc_b else 0,
                                                   wws.data_ptr() if wws is not None else None,

@@ -3,9 +3,14 @@
 Each forward/backward is one (or two) kernel launches on torch's current stream; nothing here
 synchronises with the host, so a whole training step can be captured in a HIP graph.
 """
+import warnings
+
 import torch
 
+from . import conv as _conv
 from . import lib as L
+
+_WARNED_SRC_ATOMICS = False   # PhotoLossFn.backward: the deterministic-mode warning about source gradients has been given
 
 
 def _f32c(t):
@@ -87,6 +92,12 @@ class PhotoLossFn(torch.autograd.Function):
         g_pose = torch.empty_like(pose) if need[2] else None
         g_mask = torch.empty_like(mask) if (mask is not None and need[5]) else None
         g_srcs = [torch.zeros_like(s) if need[7 + i] else None for i, s in enumerate(srcs)]
+        global _WARNED_SRC_ATOMICS
+        if _conv.DETERMINISTIC and not _WARNED_SRC_ATOMICS and any(g is not None for g in g_srcs):
+            _WARNED_SRC_ATOMICS = True
+            warnings.warn("deterministic mode: the photometric backward sums the source-image gradients (the feature term's "
+                          "feature maps) with float atomics, so the parameters trained through them are not bit-identical "
+                          "from run to run", RuntimeWarning, stacklevel=2)
         ws = torch.empty(int(lib.dvf_photo_pose_ws_floats(B, H, W, V)), device=tgt.device) if need[2] else None
         gl = _f32c(gloss).reshape(1)
         # bwd = fwd (recompute) + grad depth + mask grads + grad target + RMW scatter into the source grads

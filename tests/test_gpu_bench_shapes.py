@@ -9,7 +9,10 @@ prove the kernel variants the headline number runs on.  Here:
      record the library reports (dvf_conv2d_last_plans) is collected;
   2. every distinct convolution geometry of that step is run alone (forward, dgrad of the segments that need it, wgrad,
      bias grad) against torch CPU conv2d / conv_transpose2d at 1e-4;
-  3. the set of plans hit in 2 must contain the set the step used in 1.
+  3. the set of plans hit in 2 must contain the set the step used in 1;
+  4. deterministic mode (dvf.conv.set_deterministic): every geometry of 2 again with the ordered weight / bias reductions,
+     at 1e-4 against the same torch CPU tensors and bit-identical from run to run; per configuration, the deterministic
+     step against the default one (see test_deterministic_step_matches_default).
 Bound: 1e-4 relative (max-abs error / max-abs reference) per layer; for the step, losses at 1e-4 and gradients by
 norm at 1e-4, and by norm of the difference at max(2e-4, 8 x the fp32 oracle's own distance from an fp64 run of the
 oracle): composite gradients of the deep layers are ill-conditioned in fp32 for ANY implementation (the CPU oracle is
@@ -150,7 +153,15 @@ def _check_geometry(gi, geom, failures):
     bad = {kk: v for kk, v in errs.items() if not v < TOL}
     if bad or tuple(out.shape) != tuple(ref.shape):
         failures.append((tag, bad))
-    del out, gx, gw, gb, rx, rw, rb, ref, pre, gout
+    del out, gx, gw, gb
+
+    def plain():
+        hx = [x.clone().to(DEV).requires_grad_(ng) for x, ng in zip(xs, need_in)]
+        hw, hb = wt.clone().to(DEV).requires_grad_(True), b.clone().to(DEV).requires_grad_(True)
+        ConvFn.apply(hw, hb, cfg, *hx).backward(gout.to(DEV))
+        return hw.grad, hb.grad
+    _check_deterministic(tag, "", plain, rw.grad, rb.grad, failures)
+    del rx, rw, rb, ref, pre, gout
     # ---- the same geometry as the step runs it (dvf/conv.py::ReluTag): inputs are outputs of ReLU layers, so the
     # dgrad leaves multiplied by (x > 0); a ReLU layer itself receives dL/dpre (its consumers masked it) and its
     # bias gradient is the extra column of the weight-gradient kernel (dvf_conv2d_wgrad_bias)
@@ -183,7 +194,42 @@ def _check_geometry(gi, geom, failures):
     bad = {kk: v for kk, v in errs.items() if not v < TOL}
     if bad:
         failures.append((tag, bad))
-    del out, gx, gw, gb, rx, rw, rb, ref, pre, gout, go
+    del out, gx, gw, gb
+
+    def fused():
+        hx = [x.clone().to(DEV).requires_grad_(ng) for x, ng in zip(xs2, need_in)]
+        for x in hx:
+            x._dvf_relu_tag = ReluTag()
+        hw, hb = wt.clone().to(DEV).requires_grad_(True), b.clone().to(DEV).requires_grad_(True)
+        ConvFn.apply(hw, hb, tuple(cfg) + ((ReluTag(),) if act == 1 else ()), *hx).backward(go.to(DEV))
+        return hw.grad, hb.grad
+    _check_deterministic(tag, "fused ", fused, rw.grad, rb.grad, failures)
+    del rx, rw, rb, ref, pre, gout, go
+
+
+def _check_deterministic(tag, form, run, ref_w, ref_b, failures):
+    """Two runs of `run` (returns the weight and bias gradients of one HIP backward) under dvf.conv.set_deterministic(True):
+    ordered weight / bias reductions (wgrad_pipe slabs + wgrad_reduce_kernel, act_bwd partials + bias_finish_kernel, head
+    partials + head_wgrad_finish_kernel).  Both against the same torch CPU reference at 1e-4, and bit-identical to each
+    other.  Their plan records go to STATE['det_layer_plans']."""
+    from dvf import conv as C
+    from dvf import lib as L
+    saved = L.PLAN_LOG
+    L.PLAN_LOG = STATE.setdefault("det_layer_plans", set())
+    C.set_deterministic(True)
+    try:
+        (w1, b1), (w2, b2) = run(), run()
+    finally:
+        C.set_deterministic(False)
+        L.PLAN_LOG = saved
+    errs = {f"det {form}wgrad": rel_err(w1, ref_w), f"det {form}bias": rel_err(b1, ref_b)}
+    bad = {kk: v for kk, v in errs.items() if not v < TOL}
+    if not torch.equal(w1, w2):
+        bad[f"det {form}wgrad repeat"] = float((w1 - w2).abs().max())
+    if not torch.equal(b1, b2):
+        bad[f"det {form}bias repeat"] = float((b1 - b2).abs().max())
+    if bad:
+        failures.append((tag, bad))
 
 
 def _check_geometries(geoms, seed_base):
@@ -275,3 +321,82 @@ def test_other_bench_configs_geometries_and_plans(config):
     missing = sorted(step_plans - STATE["layer_plans"])
     assert not missing, (config, missing)
     print("cfg %d: %d geometries, %d plans, all parity-tested" % (config, len(geoms), len(step_plans)))
+
+
+# ---------------------------------------------------------------------------------------------------- deterministic mode
+# dvf.conv.set_deterministic(True) swaps every float-atomic weight / bias sum of the step for an ordered one.  Per layer,
+# _check_geometry compares those paths with torch CPU (above).  Per step, on the arena path (side streams, accumulation into
+# FlatAdam.flat_g, modules used twice), three eager passes from the same weights -- deterministic, deterministic, default --
+# must give (a) bit-identical arenas for the two deterministic passes outside the feature term's exception, (b) the default
+# arena up to reduction noise (only the summation order of weight / bias gradients differs, and those feed nothing else in
+# the step: an O(1) difference is a mapping bug), (c) ordered weight-gradient kernels only, (d) no plan the per-layer
+# deterministic checks did not run.
+DET_TOL = 1e-5         # deterministic vs default arena, per parameter (rel_err)
+DET_TOL_FEAT = 1e-4    # FeatExtractor parameters: their gradients come through the photometric kernel's atomic scatter
+
+
+def _ordered_wgrad(rec):
+    """A weight-gradient plan record (as dvf.lib.note_plans stores it: op, kernel, fields) of an ordered path: wgrad_pipe
+    with its slabs in scratch (ws bit of field 3) or the direct head kernel with its partials buffer."""
+    return (rec[1] == 8 and rec[4] & 2) or (rec[1] == 5 and rec[3] == 1)
+
+
+@pytest.mark.parametrize("config", [2, 3, 4, 5])
+def test_deterministic_step_matches_default(config):
+    import argparse
+    from dvf import conv as C
+    from dvf import lib as L
+    bench = _bench_module()
+    cfg = bench.CONFIGS[config]
+    args = argparse.Namespace(batch=cfg["batch"], height=cfg["height"], width=cfg["width"], seed=0, force_ddp=False,
+                              no_graph=True)
+    step, fwd_bwd, opt, _, nets = bench.build(args, cfg, torch.device(DEV), 1, 0)
+
+    def arena():
+        fwd_bwd()
+        L.join_aux_streams()
+        torch.cuda.synchronize()
+        return opt.flat_g.clone()
+
+    # the first deterministic pass of the process grows the side streams' scratch (dvf/conv.py::_workspace)
+    C.GEOM_LOG, L.PLAN_LOG = [], set()
+    C.set_deterministic(True)
+    try:
+        det1 = arena()
+        geoms, det_plans = _distinct(C.GEOM_LOG), L.PLAN_LOG
+        C.GEOM_LOG, L.PLAN_LOG = None, None
+        det2 = arena()
+    finally:
+        C.set_deterministic(False)
+        C.GEOM_LOG, L.PLAN_LOG = None, None
+    default = arena()
+    assert float(det1.abs().max()) > 0 and torch.isfinite(det1).all()
+    worst, worst_feat = (0.0, ""), (0.0, "")
+    for net_name, net in nets.items():
+        for k, p in net.named_parameters():
+            name = f"{net_name}.{k}"
+            sl = slice(p._dvf_offset, p._dvf_offset + p.numel())
+            a, a2, d = det1[sl], det2[sl], default[sl]
+            feat = net_name == "feat"
+            if not feat:
+                # (a) outside the feature term's source-gradient scatter (float atomics across blocks), bit identity
+                assert torch.equal(a, a2), (config, name, float((a - a2).abs().max()))
+            e = rel_err(a, d)
+            assert e <= (DET_TOL_FEAT if feat else DET_TOL), (config, name, e)
+            if feat:
+                worst_feat = max(worst_feat, (e, name))
+            else:
+                worst = max(worst, (e, name))
+    del step, fwd_bwd, opt, nets, arena, det1, det2, default
+    torch.cuda.empty_cache()
+    # (c) every weight gradient of the deterministic step went through an ordered path
+    wrecs = [r for r in det_plans if r[0] == "wgrad"]
+    assert wrecs, "the library reported no weight-gradient plans"
+    unordered = sorted(r for r in wrecs if not _ordered_wgrad(r))
+    assert not unordered, (config, unordered)
+    # (d) and through plans the per-layer deterministic checks ran against torch CPU
+    _check_geometries(geoms, 10000 * config)
+    missing = sorted(det_plans - STATE["det_layer_plans"])
+    assert not missing, (config, missing)
+    print("cfg %d deterministic vs default: worst rel_err %.2e at %s; FeatExtractor %s; %d plans" %
+          (config, worst[0], worst[1], "%.2e at %s" % worst_feat if worst_feat[1] else "-", len(det_plans)))

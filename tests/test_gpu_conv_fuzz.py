@@ -42,10 +42,8 @@ def _cases():
 CASES = _cases()
 
 
-@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
-def test_wgrad_envelope(case):
-    from dvf.conv import ConvFn, ReluTag
-    from dvf import lib as L
+def _wgrad_case(case):
+    """CPU reference of one envelope case: inputs, gout, and the weight / bias gradients of torch's conv."""
     name, segs, cout, k, stride, pad, opad, transposed, (n, h, w), fused = case
     gen = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 100000)
     cin = sum(segs)
@@ -61,6 +59,14 @@ def test_wgrad_envelope(case):
         pre = F.conv2d(xin, rw, rb, stride=stride, padding=pad)
     gout = torch.randn(pre.shape, generator=gen)
     (pre * gout).sum().backward()
+    return xs, wt, b, pre, gout, rw.grad, rb.grad
+
+
+def _hip_wgrad(case, xs, wt, b, gout):
+    """(out, weight gradient, bias gradient) of one HIP forward + backward of an envelope case."""
+    from dvf.conv import ConvFn, ReluTag
+    from dvf import lib as L
+    name, segs, cout, k, stride, pad, opad, transposed, (n, h, w), fused = case
     gx = [x.clone().to(DEV) for x in xs]
     gw, gb = wt.clone().to(DEV).requires_grad_(True), b.clone().to(DEV).requires_grad_(True)
     # fused: the layer is a ReLU layer whose consumers delivered dL/dpre (here: gout masked by relu') and whose bias gradient
@@ -68,10 +74,56 @@ def test_wgrad_envelope(case):
     act = L.ACT_RELU if fused else L.ACT_NONE
     cfg = (k, stride, pad, opad, transposed, act, 1.0, 0.0, None) + ((ReluTag(),) if fused else ())
     out = ConvFn.apply(gw, gb, cfg, *gx)
-    assert tuple(out.shape) == tuple(pre.shape), (name, out.shape, pre.shape)
     out.backward(gout.to(DEV))
-    assert rel_err(gw.grad, rw.grad) < TOL, (name, "wgrad", rel_err(gw.grad, rw.grad))
-    assert rel_err(gb.grad, rb.grad) < TOL, (name, "bias", rel_err(gb.grad, rb.grad))
+    return out, gw.grad, gb.grad
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_wgrad_envelope(case):
+    name = case[0]
+    xs, wt, b, pre, gout, rw_grad, rb_grad = _wgrad_case(case)
+    out, gw_grad, gb_grad = _hip_wgrad(case, xs, wt, b, gout)
+    assert tuple(out.shape) == tuple(pre.shape), (name, out.shape, pre.shape)
+    assert rel_err(gw_grad, rw_grad) < TOL, (name, "wgrad", rel_err(gw_grad, rw_grad))
+    assert rel_err(gb_grad, rb_grad) < TOL, (name, "bias", rel_err(gb_grad, rb_grad))
+
+
+# Envelope cases whose weight gradient runs the register-staged conv_wgrad_kernel (float atomics) even in deterministic
+# mode, because wgrad_pipe cannot take them: checked for correctness only.  Any other case leaving the ordered paths fails.
+UNORDERED_IN_DETERMINISTIC_MODE = frozenset()
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_wgrad_envelope_deterministic(case):
+    """The same geometries under dvf.conv.set_deterministic(True): wgrad_pipe slabs + wgrad_reduce_kernel (TILE 16 / 32,
+    MT / NTW variants, fewer items than blocks, 2x3 maps, 4-byte lanes, 1-3 segments, transposed layers, with and without
+    the bias column), the ordered bias sums and the head kernel's partials.  Against the same CPU reference at 1e-4; a
+    second run must be bit-identical; the plan log must name an ordered weight-gradient path."""
+    from dvf import conv as C
+    from dvf import lib as L
+    name = case[0]
+    xs, wt, b, pre, gout, rw_grad, rb_grad = _wgrad_case(case)
+    runs = []
+    C.set_deterministic(True)
+    try:
+        for _ in range(2):
+            L.PLAN_LOG = set()
+            _, gw_grad, gb_grad = _hip_wgrad(case, xs, wt, b, gout)
+            runs.append((gw_grad, gb_grad, {r for r in L.PLAN_LOG if r[0] == "wgrad"}))
+    finally:
+        C.set_deterministic(False)
+        L.PLAN_LOG = None
+    (w1, b1, plans), (w2, b2, _) = runs
+    assert rel_err(w1, rw_grad) < TOL, (name, "det wgrad", rel_err(w1, rw_grad))
+    assert rel_err(b1, rb_grad) < TOL, (name, "det bias", rel_err(b1, rb_grad))
+    assert plans, name
+    unordered = sorted(r for r in plans if not ((r[1] == 8 and r[4] & 2) or (r[1] == 5 and r[3] == 1)))
+    if name in UNORDERED_IN_DETERMINISTIC_MODE:
+        assert unordered, (name, "now runs an ordered path: remove it from UNORDERED_IN_DETERMINISTIC_MODE", sorted(plans))
+        return
+    assert not unordered, (name, unordered)
+    assert torch.equal(w1, w2), (name, "det wgrad repeat", float((w1 - w2).abs().max()))
+    assert torch.equal(b1, b2), (name, "det bias repeat", float((b1 - b2).abs().max()))
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])

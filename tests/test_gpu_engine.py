@@ -1,7 +1,7 @@
 """GPU tests of the training-step engine (dvf/engine.py) beyond the golden steps:
  * a module applied TWICE per step (shared weights: two gradient contributions per parameter) must not let its bucket
    leave -- all-reduce, Adam, repack -- after the first contribution: three iterations against the CPU oracle, with the
-   early per-bucket update and the exchange path on;
+   early per-bucket update and the exchange path on, with float-atomic and with ordered (deterministic) gradient sums;
  * packed weight copies used by EAGER code between HIP-graph replays (validate() with a batch size the capture never saw)
    must follow the weights the replays update."""
 import pytest
@@ -37,9 +37,13 @@ def _oracle_twice(sd, x1, x2, w1, w2, steps, lr):
     return losses, {k: v.detach() for k, v in params.items()}
 
 
-@pytest.mark.parametrize("early", [True, False])
-def test_module_used_twice_per_step_tracks_oracle(early):
+# (ids "True" / "False": the default mode, as before; "-det": dvf.conv.set_deterministic(True), where the second contribution
+# of each parameter is a second ordered reduce into the same arena slice)
+@pytest.mark.parametrize("early,det", [pytest.param(True, False, id="True"), pytest.param(False, False, id="False"),
+                                       pytest.param(True, True, id="True-det"), pytest.param(False, True, id="False-det")])
+def test_module_used_twice_per_step_tracks_oracle(early, det):
     import DispNetS
+    from dvf import conv as C
     from dvf.engine import FlatAdam
     torch.manual_seed(3)
     h, w, steps, lr = 64, 128, 3, 1e-3
@@ -57,15 +61,19 @@ def test_module_used_twice_per_step_tracks_oracle(early):
     gx1, gx2 = x1.to(DEV), x2.to(DEV)
     gw1, gw2 = [v.to(DEV) for v in w1], [v.to(DEV) for v in w2]
     losses, launched_in_backward = [], []
-    for _ in range(steps):
-        o1, o2 = net(gx1), net(gx2)
-        loss = sum((o * v).sum() for o, v in zip(o1, gw1)) + sum((o * v).sum() for o, v in zip(o2, gw2))
-        opt.zero_grad()
-        loss.backward()
-        launched_in_backward.append(sum(1 for b in opt.buckets if b["launched"]))
-        opt.step()
-        losses.append(float(loss))
-    torch.cuda.synchronize()
+    C.set_deterministic(det)
+    try:
+        for _ in range(steps):
+            o1, o2 = net(gx1), net(gx2)
+            loss = sum((o * v).sum() for o, v in zip(o1, gw1)) + sum((o * v).sum() for o, v in zip(o2, gw2))
+            opt.zero_grad()
+            loss.backward()
+            launched_in_backward.append(sum(1 for b in opt.buckets if b["launched"]))
+            opt.step()
+            losses.append(float(loss))
+        torch.cuda.synchronize()
+    finally:
+        C.set_deterministic(False)
     for p in opt.params:
         assert p._dvf_expect == 2, "every DispNetS parameter receives two contributions per step"
     if early:
