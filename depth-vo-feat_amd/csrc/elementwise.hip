@@ -174,10 +174,14 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float *partials
     }
 }
 
+// aten's binary_cross_entropy backward with target 1: g * (m - 1) / max((1 - m) * m, 1e-12).  Not the derivative of the
+// clamped forward: below m = 1e-12 (exact zeros included) the gradient stays at -1e12 g, and at m = 1 it is 0.
 __global__ void bce_ones_bwd_kernel(const float *m, const float *grad_loss, float *gm, int64_t n) {
     const float g = grad_loss[0] / (float)n;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        gm[i] = (logf(m[i]) > -100.f) ? -g / m[i] : 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float v = m[i];
+        gm[i] = g * (v - 1.f) / fmaxf((1.f - v) * v, 1e-12f);
+    }
 }
 
 // Depthwise ConvTranspose2d(C, C, k=4, stride=2, pad=1, groups=C) (+ residual add): feat_extractor.py:38-41,72-82.
@@ -271,8 +275,11 @@ __global__ __launch_bounds__(256) void dwconvt_wgrad_kernel(const float *x, cons
     __syncthreads();
     if (threadIdx.x < 17) {
         const float r = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-        if (threadIdx.x < 16) atomicAdd(&dw[c * 16 + threadIdx.x], r);
-        else if (db) atomicAdd(&db[c], r);
+        if (threadIdx.x < 16) {
+            if (dw) atomicAdd(&dw[c * 16 + threadIdx.x], r);
+        } else if (db) {
+            atomicAdd(&db[c], r);
+        }
     }
 }
 
@@ -359,8 +366,8 @@ int dvf_dwconvt4x4s2_bwd(const float *x, const float *w, const float *dy, float 
         dwconvt_dgrad_kernel<<<nblocks(total), 256, 0, st>>>(dy, w, dx, C, H, W, total);
         DVF_LAUNCH_CHECK();
     }
-    if (dw) {
-        if (hipMemsetAsync(dw, 0, sizeof(float) * 16 * C, st) != hipSuccess) return DVF_ERR_LAUNCH;
+    if (dw || db) {                      // one pass yields both; either may be wanted alone (a frozen weight, a trained bias)
+        if (dw && hipMemsetAsync(dw, 0, sizeof(float) * 16 * C, st) != hipSuccess) return DVF_ERR_LAUNCH;
         if (db && hipMemsetAsync(db, 0, sizeof(float) * C, st) != hipSuccess) return DVF_ERR_LAUNCH;
         int chunks = (H * W + 2047) / 2048;
         while (chunks > 1 && (int64_t)N * C * chunks > 8192) chunks >>= 1;

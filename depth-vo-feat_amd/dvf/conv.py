@@ -475,11 +475,15 @@ class DepthwiseUp2xFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, skip):
         ctx.wparam = weight if getattr(weight, "_dvf_grad", None) is not None else None
         ctx.bparam = bias if getattr(bias, "_dvf_grad", None) is not None else None
-        x, weight, bias, skip = _c(x), _c(weight), _c(bias), _c(skip)
+        x, weight = _c(x), _c(weight)
+        bias = _c(bias) if bias is not None else None          # (the kernel takes either as optional)
+        skip = _c(skip) if skip is not None else None
         N, C, H, W = x.shape
-        if tuple(skip.shape) != (N, C, 2 * H, 2 * W) or tuple(weight.shape) != (C, 1, 4, 4):
-            raise ValueError(f"shape mismatch: x {tuple(x.shape)} weight {tuple(weight.shape)} skip {tuple(skip.shape)}")
-        out = torch.empty_like(skip)
+        if (skip is not None and tuple(skip.shape) != (N, C, 2 * H, 2 * W)) or tuple(weight.shape) != (C, 1, 4, 4) or \
+                (bias is not None and tuple(bias.shape) != (C,)):
+            raise ValueError(f"shape mismatch: x {tuple(x.shape)} weight {tuple(weight.shape)} "
+                             f"bias {None if bias is None else tuple(bias.shape)} skip {None if skip is None else tuple(skip.shape)}")
+        out = torch.empty((N, C, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
         L.check(L.lib().dvf_dwconvt4x4s2_fwd(L.dev(x, "input"), L.dev(weight, "weight"), L.dev(bias, "bias"),
                                              L.dev(skip, "skip"), L.dev(out), N, C, H, W, L.stream()), "dvf_dwconvt4x4s2_fwd")
         ctx.save_for_backward(x, weight)
@@ -492,7 +496,7 @@ class DepthwiseUp2xFn(torch.autograd.Function):
         gout = _c(gout)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(weight) if ctx.needs_input_grad[1] else None
-        db = torch.empty(C, device=x.device) if (dw is not None and ctx.needs_input_grad[2]) else None
+        db = torch.empty(C, device=x.device) if ctx.needs_input_grad[2] else None
         L.check(L.lib().dvf_dwconvt4x4s2_bwd(L.dev(x), L.dev(weight), L.dev(gout, "grad_out"), L.dev(dx), L.dev(dw), L.dev(db),
                                              N, C, H, W, L.stream()), "dvf_dwconvt4x4s2_bwd")
         if dw is not None and ctx.wparam is not None:

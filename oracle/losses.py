@@ -87,13 +87,14 @@ def photometric_reconstruction_loss_sfm(tgt_img, ref_imgs, intrinsics, intrinsic
 
 
 def explainability_loss(mask):
-    """sum_s BCE(mask_s, 1) = sum_s -mean(log mask_s) (torch clamps log at -100).
-    loss_functions_sfm.py:49-56."""
+    """sum_s BCE(mask_s, 1): the reference's own call (loss_functions_sfm.py:49-56).  The value is
+    -mean(max(log m, -100)); the gradient is aten's, g (m - 1) / max((1 - m) m, 1e-12) / numel, which is
+    -1e12 g / numel below m = 1e-12 (exact zeros included) and 0 at m = 1."""
     if type(mask) not in (tuple, list):
         mask = [mask]
     loss = 0
     for m in mask:
-        loss = loss + (-torch.clamp(torch.log(m), min=-100.0)).mean()
+        loss = loss + F.binary_cross_entropy(m, torch.ones_like(m))
     return loss
 
 

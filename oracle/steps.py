@@ -2,9 +2,11 @@
 
   adam_step          torch.optim.Adam as configured at train.py:150-156 / unsupervise.py:241
                      (L2-in-gradient weight decay, bias correction, eps outside the sqrt)
+  unsupervise_terms  the loss of step_unsupervise from the networks' outputs (tests feed it fixed ones)
   step_unsupervise   unsupervise.py:83-120 with PoseExpNet substituted for FixOdometryNet
                      (north_star; FixOdometryNet is the out-of-scope fixed-point stack) and
                      disp[0] used where unsupervise.py:99 would break on DispNetS' list output
+  train_sfm_terms    the loss of step_train_sfm from the networks' outputs
   step_train_sfm     train.py:179-214 (DispNetS + PoseExpNet_sfm, 4-scale photometric with masks,
                      smooth, stereo-pose MSE)
 
@@ -64,17 +66,11 @@ def _leaf(sd):
     return {k: v.detach().clone().requires_grad_(True) for k, v in sd.items()}
 
 
-def step_unsupervise(disp_sd, pose_sd, batch, adam_state=None, lr=1e-3, weight_decay=1e-8,
-                     img_scale=0.004, smooth_weight=10.0, feat_sd=None, feat_weight=0.1,
-                     do_update=True, dvo=False):
-    """One unsupervise.py iteration.  Returns dict(losses, grads) and updates the dicts in place.  dvo=True swaps the
-    image term for the unsupervise_dvo.py chain (se3 exponential map + pixel-coordinate warp, batch["T_R2L"] then in
-    (w, u) order)."""
-    dsd, psd = _leaf(disp_sd), _leaf(pose_sd)
-    fsd = _leaf(feat_sd) if feat_sd is not None else None
+def unsupervise_terms(batch, disp, T_2to1, feat=None, img_scale=0.004, smooth_weight=10.0, feat_weight=0.1, dvo=False):
+    """The loss of one unsupervise.py iteration (:99-111) from the networks' outputs: the finest disparity [B,1,H,W],
+    T_2to1 [B,6] and, for the feature term, FeatExtractor's maps of cat(L2, R2, R1) [3B,32,H,W].
+    Returns (total, dict of detached terms)."""
     R2, R1, L2 = batch["img_R2"], batch["img_R1"], batch["img_L2"]
-    disp = nets.dispnet_forward(dsd, R2)[0]                                   # unsupervise.py:94
-    _, T_2to1 = nets.posenet_forward(psd, torch.cat((R2, R1), 1), 2, True, sfm=False)   # :92,95
     depth = (1 / (disp + 1e-4)).squeeze(1)                                    # :99
     if dvo:
         from . import geometry
@@ -87,15 +83,31 @@ def step_unsupervise(disp_sd, pose_sd, batch, adam_state=None, lr=1e-3, weight_d
     smooth = losses.smooth_loss(depth.unsqueeze(1))                           # :102
     total = img_loss + smooth_weight * smooth
     out = {"img": img_loss.detach(), "smooth": smooth.detach()}
-    if fsd is not None:
+    if feat is not None:
         b = R2.shape[0]
-        feat = nets.featnet_forward(fsd, torch.cat((L2, R2, R1), 0))          # :104-105
         f_L2, f_R2, f_R1 = feat[:b], feat[b:2 * b], feat[2 * b:]              # :107
         feat_loss = losses.photometric_reconstruction_loss(f_R2, f_R1, f_L2, depth, T_2to1,
                                                            batch["T_R2L"], batch["K"], batch["Kinv"])  # :109
         total = total + feat_weight * feat_loss                               # :111
         out["feat"] = feat_loss.detach()
     out["total"] = total.detach()
+    return total, out
+
+
+def step_unsupervise(disp_sd, pose_sd, batch, adam_state=None, lr=1e-3, weight_decay=1e-8,
+                     img_scale=0.004, smooth_weight=10.0, feat_sd=None, feat_weight=0.1,
+                     do_update=True, dvo=False):
+    """One unsupervise.py iteration.  Returns dict(losses, grads) and updates the dicts in place.  dvo=True swaps the
+    image term for the unsupervise_dvo.py chain (se3 exponential map + pixel-coordinate warp, batch["T_R2L"] then in
+    (w, u) order)."""
+    dsd, psd = _leaf(disp_sd), _leaf(pose_sd)
+    fsd = _leaf(feat_sd) if feat_sd is not None else None
+    R2, R1, L2 = batch["img_R2"], batch["img_R1"], batch["img_L2"]
+    disp = nets.dispnet_forward(dsd, R2)[0]                                   # unsupervise.py:94
+    _, T_2to1 = nets.posenet_forward(psd, torch.cat((R2, R1), 1), 2, True, sfm=False)   # :92,95
+    feat = nets.featnet_forward(fsd, torch.cat((L2, R2, R1), 0)) if fsd is not None else None   # :104-105
+    total, out = unsupervise_terms(batch, disp, T_2to1, feat, img_scale=img_scale, smooth_weight=smooth_weight,
+                                   feat_weight=feat_weight, dvo=dvo)
     total.backward()
     groups = [("pose", pose_sd, psd), ("disp", disp_sd, dsd)] + ([("feat", feat_sd, fsd)] if fsd is not None else [])
     grads = {g: {k: v.grad for k, v in leaf.items() if v.grad is not None} for g, _, leaf in groups}
@@ -155,6 +167,34 @@ def loss_only(batch, depth, T_2to1, img_scale=0.004, smooth_weight=10.0):
     return l.detach(), depth.grad, T.grad
 
 
+def train_sfm_terms(batch, disps, masks, pose, feat=None, w1=1.0, w2=0.0, w3=0.1, smooth_factor=2.0, nb_ref_imgs=2,
+                    rotation_mode="euler", padding_mode="zeros", feat_weight=0.1):
+    """The loss of one train.py iteration (:188-203) from the networks' outputs: DispNetS' 4 disparities, PoseExpNet_sfm's
+    4 masks and pose [B,nb_ref_imgs,6] and, for cfg 4's feature term, FeatExtractor's maps of cat(L2, R2, R1) [3B,32,H,W].
+    Returns (total, dict of detached terms)."""
+    tgt = batch["img_R2"]
+    refs = [batch["img_R1"], batch["img_L2"]] + list(batch.get("extra_refs", []))[: nb_ref_imgs - 2]
+    depth = [1 / d for d in disps]                                            # :188
+    l1 = losses.photometric_reconstruction_loss_sfm(tgt, refs, batch["K"], batch["Kinv"], depth, masks,
+                                                    pose, rotation_mode, padding_mode)   # :191
+    l2 = losses.explainability_loss(masks) if w2 > 0 else 0                   # :195-198
+    l3 = losses.smooth_loss(depth, smooth_factor)                             # :200
+    l4 = F.mse_loss(pose[:, 1], batch["T_R2L"])                               # :201
+    total = w1 * l1 + w2 * l2 + w3 * l3 + l4                                  # :203
+    out = {"photo": l1.detach(), "smooth": l3.detach(), "lr": l4.detach()}
+    if w2 > 0:
+        out["exp"] = l2.detach()
+    if feat is not None:
+        b = tgt.shape[0]
+        f_L2, f_R2, f_R1 = feat[:b], feat[b:2 * b], feat[2 * b:]              # (L2, R2, R1) as unsupervise.py:104
+        lf = losses.photometric_reconstruction_loss(f_R2, f_R1, f_L2, depth[0].squeeze(1), pose[:, 0], pose[:, 1],
+                                                    batch["K"], batch["Kinv"], rotation_mode, padding_mode)
+        total = total + feat_weight * lf
+        out["feat"] = lf.detach()
+    out["total"] = total.detach()
+    return total, out
+
+
 def step_train_sfm(disp_sd, pose_sd, batch, adam_state=None, lr=2e-4, w1=1.0, w2=0.0, w3=0.1,
                    smooth_factor=2.0, nb_ref_imgs=2, rotation_mode="euler", padding_mode="zeros",
                    do_update=True, feat_sd=None, feat_weight=0.1):
@@ -166,26 +206,11 @@ def step_train_sfm(disp_sd, pose_sd, batch, adam_state=None, lr=2e-4, w1=1.0, w2
     tgt = batch["img_R2"]
     refs = [batch["img_R1"], batch["img_L2"]] + list(batch.get("extra_refs", []))[: nb_ref_imgs - 2]
     disps = nets.dispnet_forward(dsd, tgt)                                    # :187
-    depth = [1 / d for d in disps]                                            # :188
     masks, pose = nets.posenet_forward(psd, torch.cat([tgt] + refs, 1), nb_ref_imgs, True, sfm=True)  # :189
-    l1 = losses.photometric_reconstruction_loss_sfm(tgt, refs, batch["K"], batch["Kinv"], depth, masks,
-                                                    pose, rotation_mode, padding_mode)   # :191
-    l2 = losses.explainability_loss(masks) if w2 > 0 else 0                   # :195-198
-    l3 = losses.smooth_loss(depth, smooth_factor)                             # :200
-    l4 = F.mse_loss(pose[:, 1], batch["T_R2L"])                               # :201
-    total = w1 * l1 + w2 * l2 + w3 * l3 + l4                                  # :203
-    out = {"photo": l1.detach(), "smooth": l3.detach(), "lr": l4.detach()}
-    if w2 > 0:
-        out["exp"] = l2.detach()
-    if fsd is not None:
-        b = tgt.shape[0]
-        feat = nets.featnet_forward(fsd, torch.cat((refs[1], tgt, refs[0]), 0))          # (L2, R2, R1) as unsupervise.py:104
-        f_L2, f_R2, f_R1 = feat[:b], feat[b:2 * b], feat[2 * b:]
-        lf = losses.photometric_reconstruction_loss(f_R2, f_R1, f_L2, depth[0].squeeze(1), pose[:, 0], pose[:, 1],
-                                                    batch["K"], batch["Kinv"], rotation_mode, padding_mode)
-        total = total + feat_weight * lf
-        out["feat"] = lf.detach()
-    out["total"] = total.detach()
+    feat = nets.featnet_forward(fsd, torch.cat((refs[1], tgt, refs[0]), 0)) if fsd is not None else None
+    total, out = train_sfm_terms(batch, disps, masks, pose, feat, w1=w1, w2=w2, w3=w3, smooth_factor=smooth_factor,
+                                 nb_ref_imgs=nb_ref_imgs, rotation_mode=rotation_mode, padding_mode=padding_mode,
+                                 feat_weight=feat_weight)
     total.backward()
     groups = [("disp", disp_sd, dsd), ("pose", pose_sd, psd)] + ([("feat", feat_sd, fsd)] if fsd is not None else [])
     grads = {g: {k: v.grad for k, v in leaf.items() if v.grad is not None} for g, _, leaf in groups}

@@ -277,12 +277,70 @@ def test_bench_plans_are_the_tested_plans():
 # ---------------------------------------------------------------------------------------------------- cfg 3 / 4 / 5
 # The other benchmark configurations (bench.CONFIGS): FeatExtractor on 3 x 8 full-resolution images
 # (reference: unsupervise.py:104-111), the 4-scale train.py body with the feature term, and 384x1280 with a five-frame
-# window (PoseExpNet_sfm.py:22-36: a 15-channel first convolution; loss_functions_sfm.py:9-46 with V = 4).  A full-size
-# ORACLE step of these is minutes of CPU time per configuration; the body arithmetic is pinned at reduced size
-# (tests/test_gpu_nets.py, golden steps).  What is shape dependent -- the convolution plans and the fused loss kernels'
-# size-dependent paths -- is pinned here: one full-size step per configuration collects every convolution geometry and
-# every plan record; each geometry not seen before is parity-checked against torch CPU at 1e-4 (plain and fused forms);
-# the step's plans must be a subset of the parity-checked plans; the step's loss must be finite.
+# window (PoseExpNet_sfm.py:22-36: a 15-channel first convolution; loss_functions_sfm.py:9-46 with V = 4).  One full-size
+# step per configuration collects every convolution geometry and every plan record; each geometry not seen before is
+# parity-checked against torch CPU at 1e-4 (plain and fused forms); the step's plans must be a subset of the
+# parity-checked plans.  The step itself -- every loss term and every parameter's gradient in FlatAdam's arena -- is
+# compared with a full-size oracle step from the same weights and batch, in fp32 and in fp64 (about 10-35 s of CPU time
+# each, up to ~23 GB of host memory for cfg 5 in fp64), with the bound shape of test_fullsize_step_vs_oracle.  A few
+# gradients are sums over millions of pixels that cancel: the fp32 oracle itself is more than 1e-2 away from fp64 there
+# (CANCELLING), so only their distance from fp64 is bounded, against the fp32 oracle's; tests/test_gpu_bench_kernels.py
+# checks the kernels behind them directly.
+CANCELLING = {3: {"feat.conv_3_bb4_up.bias"}, 4: set(), 5: set()}
+LOSS_FLOOR_FACTOR = 4
+
+
+def _oracle_step(cfg, sds, dtype):
+    """(loss terms, {net: {param: grad}}) of the full-size oracle step of one configuration in `dtype`."""
+    b = osteps.synthetic_batch(cfg["batch"], cfg["height"], cfg["width"], seed=1234, n_views=cfg["nb_ref"])
+    b = {k: ([x.to(dtype) for x in v] if isinstance(v, list) else v.to(dtype)) for k, v in b.items()}
+    sd = {n: {k: v.to(dtype) for k, v in d.items()} for n, d in sds.items()}
+    if cfg["body"] == "unsupervise":
+        out, grads, _ = osteps.step_unsupervise(sd["disp"], sd["pose"], b, feat_sd=sd.get("feat"), do_update=False)
+    else:
+        out, grads, _ = osteps.step_train_sfm(sd["disp"], sd["pose"], b, feat_sd=sd.get("feat"), nb_ref_imgs=cfg["nb_ref"],
+                                              do_update=False)
+    return {k: float(v) for k, v in out.items()}, grads
+
+
+def _check_step_vs_oracle(config, cfg, terms, grads, sds):
+    """terms: the HIP step's loss terms (floats); grads: {"net.param": HIP gradient (CPU)}; sds: the networks' state dicts
+    (CPU).  Returns the worst ratio of a gradient's distance to its bound."""
+    ref, g32 = _oracle_step(cfg, sds, torch.float32)
+    ref64, g64 = _oracle_step(cfg, sds, torch.float64)
+    failures = []
+    for k, v in terms.items():
+        floor = abs(ref[k] - ref64[k]) / abs(ref64[k])
+        if not (abs(v - ref[k]) <= TOL * abs(ref[k]) or
+                abs(v - ref64[k]) <= max(TOL, LOSS_FLOOR_FACTOR * floor) * abs(ref64[k])):
+            failures.append((k, v, ref[k], ref64[k]))
+    worst = (0.0, "", 0.0)
+    for name, g in grads.items():
+        net, k = name.split(".", 1)
+        if k not in g32[net]:
+            if float(g.abs().max()) != 0.0:
+                failures.append((name, "gradient where the oracle has none"))
+            continue
+        g = g.double()
+        r, r64 = g32[net][k].double(), g64[net][k]
+        rn = max(float(r.norm()), 1e-30)
+        floor = float((r - r64).norm()) / rn
+        if name in CANCELLING[config]:
+            # a cancelling sum: no further from fp64 than 8x the fp32 oracle, plus 1e-4 of the fp64 norm
+            if not float((g - r64).norm()) <= 8 * float((r - r64).norm()) + 1e-4 * float(r64.norm()):
+                failures.append((name, "cancelling", float((g - r64).norm()), float((r - r64).norm())))
+            continue
+        # norm and direction, both within max(2e-4, 8 x floor), floor = |g32 - g64| / |g32| (the cfg-2 bound)
+        bound = max(2e-4, 8 * floor)
+        e_norm, e_norm64 = abs(float(g.norm()) - rn) / rn, abs(float(g.norm()) - float(r64.norm())) / rn
+        e_diff, e64 = float((g - r).norm()) / rn, float((g - r64).norm()) / rn
+        if not (e_norm < TOL or e_norm64 < bound) or not (e_diff < bound and e64 < bound):
+            failures.append((name, e_norm, e_norm64, e_diff, e64, floor))
+        worst = max(worst, (max(e_diff, e64) / bound, name, floor))
+    assert not failures, (config, failures)
+    return worst
+
+
 def _bench_module():
     import importlib.util
     import os
@@ -303,10 +361,19 @@ def test_other_bench_configs_geometries_and_plans(config):
     args = argparse.Namespace(batch=cfg["batch"], height=cfg["height"], width=cfg["width"], seed=0, force_ddp=False,
                               no_graph=True)
     step, fwd_bwd, opt, _, nets = bench.build(args, cfg, torch.device(DEV), 1, 0)
+    # the same batch as bench.build's (dvf.synthetic); the oracle builds its own from its own copy of the recipe
+    from dvf.synthetic import synthetic_batch
+    mine = synthetic_batch(cfg["batch"], cfg["height"], cfg["width"], seed=1234, n_views=cfg["nb_ref"])
+    theirs = osteps.synthetic_batch(cfg["batch"], cfg["height"], cfg["width"], seed=1234, n_views=cfg["nb_ref"])
+    for k, v in theirs.items():
+        assert all(torch.equal(a, b) for a, b in zip(v, mine[k])) if isinstance(v, list) else torch.equal(v, mine[k]), k
+    assert len(theirs["extra_refs"]) == len(mine["extra_refs"]) == cfg["nb_ref"] - 2
+    del mine, theirs
+    sds = {n: {k: v.detach().cpu().clone() for k, v in net.state_dict().items()} for n, net in nets.items()}
     fwd_bwd()                                         # (first pass: packs, workspaces)
     C.GEOM_LOG, L.PLAN_LOG = [], set()
     try:
-        total = fwd_bwd()[0]
+        total, terms = fwd_bwd()
         L.join_aux_streams()
         torch.cuda.synchronize()
     finally:
@@ -314,6 +381,9 @@ def test_other_bench_configs_geometries_and_plans(config):
         C.GEOM_LOG, L.PLAN_LOG = None, None
     assert torch.isfinite(total).all(), float(total)
     assert float(opt.flat_g.abs().max()) > 0 and torch.isfinite(opt.flat_g).all()
+    terms = {k: float(v) for k, v in terms.items()}
+    grads = {f"{n}.{k}": opt.flat_g[p._dvf_offset:p._dvf_offset + p.numel()].view(p.shape).cpu()
+             for n, net in nets.items() for k, p in net.named_parameters()}
     del step, fwd_bwd, opt, nets
     torch.cuda.empty_cache()
     assert geoms and step_plans
@@ -321,6 +391,8 @@ def test_other_bench_configs_geometries_and_plans(config):
     missing = sorted(step_plans - STATE["layer_plans"])
     assert not missing, (config, missing)
     print("cfg %d: %d geometries, %d plans, all parity-tested" % (config, len(geoms), len(step_plans)))
+    ratio, name, floor = _check_step_vs_oracle(config, cfg, terms, grads, sds)
+    print("cfg %d vs oracle: worst gradient at %.2f of its bound, %s (fp32 oracle floor %.2e)" % (config, ratio, name, floor))
 
 
 # ---------------------------------------------------------------------------------------------------- deterministic mode

@@ -121,6 +121,10 @@ def _kitti_K(b, h, w):
     (4, 3, 256, 832, "euler", "zeros", False, 2),      # BASELINE cfg 2 size, full batch
     (8, 32, 256, 832, "euler", "zeros", False, 2),     # cfg 3's feature term at its bench size (C = 32, batch 8, all gradients)
     (2, 3, 384, 1280, "euler", "zeros", False, 4),     # cfg 5's finest scale: five-frame window (V = 4) with masks, 384x1280
+    (8, 3, 384, 1280, "euler", "zeros", False, 4),     # ... at cfg 5's real batch
+    (4, 3, 64, 208, "euler", "zeros", False, 2),       # cfg 4's third scale (V = 2, masks)
+    (8, 3, 96, 320, "euler", "zeros", False, 4),       # cfg 5's coarse scales (V = 4, masks)
+    (8, 3, 48, 160, "euler", "zeros", False, 4),
 ])
 def test_photometric_vs_oracle(b, c, h, w, rot, pad, align, v):
     """Fused kernel vs the oracle on seeded random inputs, explainability-mask form (pose [B,V,6]).
@@ -324,3 +328,164 @@ def test_dvo_front_end_vs_oracle():
     assert rel_err(out, ref) < TOL
     assert outliers(gd.grad, cpu[0].grad, TOL) <= 4
     assert rel_err(gp.grad[0], cpu[1].grad) < TOL and rel_err(gp.grad[1], cpu[2].grad) < TOL
+
+
+# ---------------------------------------------------------------------------------------------------- bench-size loss stage
+# The loss stage of the cfg 3 / 4 / 5 steps from IDENTICAL inputs: the HIP networks run once at the bench size, their outputs
+# become leaf tensors, and the product's composition (dvf.steps.unsupervise_losses / train_sfm_losses, fed by stub modules
+# that return those leaves) is compared with the oracle's (oracle.steps.unsupervise_terms / train_sfm_terms) in fp32 and
+# fp64.  Without the networks' own fp32 noise this pins the composition: the per-scale area pyramid, the per-scale
+# intrinsics, the mask / view indexing at V = 4 and the feature term at batch 8.
+class _Stub(torch.nn.Module):
+    def __init__(self, out, nb_ref_imgs=None):
+        super().__init__()
+        self.out, self.nb_ref_imgs = out, nb_ref_imgs
+
+    def forward(self, *args):
+        return self.out
+
+
+def _bench_cfg(config):
+    from test_gpu_bench_shapes import _bench_module
+    return _bench_module().CONFIGS[config]
+
+
+def _net_outputs(cfg, batch):
+    """The HIP networks of one configuration (constructed and seeded as bench.build does), run once: dict of detached
+    outputs on the GPU."""
+    import DispNetS
+    torch.manual_seed(0)
+    disp = DispNetS.DispNetS()
+    if cfg["body"] == "unsupervise":
+        import PoseExpNet
+        pose = PoseExpNet.PoseExpNet(output_exp=True)
+    else:
+        import PoseExpNet_sfm
+        pose = PoseExpNet_sfm.PoseExpNet(nb_ref_imgs=cfg["nb_ref"], output_exp=True)
+    feat = None
+    if cfg["feat"]:
+        import feat_extractor
+        feat = feat_extractor.FeatExtractor()
+    for n in [pose, disp] + ([feat] if feat is not None else []):
+        n.init_weights()
+        n.to(DEV).train()
+    tgt = batch["img_R2"]
+    refs = [batch["img_R1"], batch["img_L2"]] + list(batch["extra_refs"])
+    with torch.no_grad():
+        out = {"disps": [d.detach() for d in disp(tgt)]}
+        if cfg["body"] == "unsupervise":
+            out["pose"] = pose((tgt, refs[0]))[1].detach()
+        else:
+            masks, p = pose(tgt, refs)
+            out["masks"], out["pose"] = [m.detach() for m in masks], p.detach()
+        if feat is not None:
+            out["feat"] = feat(torch.cat((refs[1], tgt, refs[0]), 0)).detach()
+    torch.cuda.synchronize()
+    return out
+
+
+def _leaves(out, device, dtype):
+    """(list of leaf tensors, the same structure rebuilt from them) on `device` in `dtype`."""
+    flat, rebuilt = [], {}
+    for k, v in out.items():
+        items = v if isinstance(v, list) else [v]
+        ls = [x.to(device=device, dtype=dtype).clone().requires_grad_(True) for x in items]
+        flat += [(f"{k}{i}" if isinstance(v, list) else k, x) for i, x in enumerate(ls)]
+        rebuilt[k] = ls if isinstance(v, list) else ls[0]
+    return flat, rebuilt
+
+
+@pytest.mark.parametrize("config", [3, 4, 5])
+def test_bench_loss_stage_vs_oracle(config):
+    """Loss terms within 1e-5 of the fp64 oracle.  Gradients with respect to pose, masks and feature maps within 1e-4 of the
+    fp32 oracle or within max(1e-4, 2 x the fp32 oracle's own distance) of fp64 (as test_photometric_vs_oracle); the
+    per-pixel disparity gradients, discontinuous where a bilinear tap set changes, by the number of pixels off by more
+    than 1e-4 (outliers()).  cfg 5 also runs explainability_loss on its four mask scales (8x4x384x1280 at the finest)."""
+    import loss_functions_sfm as LS
+    from dvf import steps as S
+    from dvf.synthetic import synthetic_batch
+    from oracle import steps as osteps
+    cfg = _bench_cfg(config)
+    b, h, w, nb = cfg["batch"], cfg["height"], cfg["width"], cfg["nb_ref"]
+    batch = synthetic_batch(b, h, w, seed=1234, device=DEV, n_views=nb)
+    nout = _net_outputs(cfg, batch)
+    flat, lv = _leaves(nout, DEV, torch.float32)
+    if cfg["body"] == "unsupervise":
+        loss, terms = S.unsupervise_losses(_Stub(lv["disps"]), _Stub((None, lv["pose"])), batch,
+                                           feat_extractor=_Stub(lv["feat"]) if "feat" in lv else None)
+    else:
+        loss, terms = S.train_sfm_losses(_Stub(lv["disps"]), _Stub((lv["masks"], lv["pose"]), nb_ref_imgs=nb), batch,
+                                         feat_extractor=_Stub(lv["feat"]) if "feat" in lv else None)
+    loss.backward()
+    torch.cuda.synchronize()
+    got = {n: x.grad.cpu() if x.grad is not None else None for n, x in flat}
+    terms = {k: float(v) for k, v in terms.items()}
+    exp_masks = [m.detach().clone().requires_grad_(True) for m in lv["masks"]] if "masks" in lv else None
+    if exp_masks is not None:
+        le = LS.explainability_loss(exp_masks)
+        le.backward()
+        le, g_exp = float(le), [m.grad.cpu() for m in exp_masks]
+    del loss, lv, flat, batch
+    nout = {k: ([x.cpu() for x in v] if isinstance(v, list) else v.cpu()) for k, v in nout.items()}
+    torch.cuda.empty_cache()
+
+    def oracle(dt):
+        ob = synthetic_batch(b, h, w, seed=1234, n_views=nb)
+        ob = {k: ([x.to(dt) for x in v] if isinstance(v, list) else v.to(dt)) for k, v in ob.items()}
+        fl, o = _leaves(nout, "cpu", dt)
+        if cfg["body"] == "unsupervise":
+            total, out = osteps.unsupervise_terms(ob, o["disps"][0], o["pose"], o.get("feat"))
+        else:
+            total, out = osteps.train_sfm_terms(ob, o["disps"], o["masks"], o["pose"], o.get("feat"), nb_ref_imgs=nb)
+        total.backward()
+        res = ({k: float(v) for k, v in out.items()}, {n: x.grad for n, x in fl})
+        if "masks" in o:
+            ms = [m.detach().clone().requires_grad_(True) for m in o["masks"]]
+            e = ol.explainability_loss(ms)
+            e.backward()
+            res += (float(e), [m.grad for m in ms])
+        return res
+
+    r32 = oracle(torch.float32)
+    r64 = oracle(torch.float64)
+    failures = []
+    for k, v in terms.items():
+        # 1e-5 of the fp32 oracle, or of fp64 within max(1e-5, 2 x the fp32 oracle's own distance): at cfg 3 the image
+        # term of the fp32 oracle is 1e-3 from fp64 (border pixels at the |x_n| = 1 overwrite, see below)
+        floor = abs(r32[0][k] - r64[0][k]) / abs(r64[0][k])
+        if not (abs(v - r32[0][k]) <= 1e-5 * abs(r32[0][k]) or abs(v - r64[0][k]) <= max(1e-5, 2 * floor) * abs(r64[0][k])):
+            failures.append((k, v, r32[0][k], r64[0][k]))
+    worst, worst_px = (0.0, ""), (0.0, "")
+    for n, g in got.items():
+        r, rr = r32[1][n], r64[1][n]
+        if rr is None:
+            if not (g is None or float(g.abs().max()) == 0.0):
+                failures.append((n, "gradient where the oracle has none"))
+            continue
+        if g is None:
+            failures.append((n, "no gradient"))
+            continue
+        floor = rel_err(r, rr)
+        e32, e64 = rel_err(g, r), rel_err(g, rr)
+        if e32 < TOL or e64 < max(TOL, 2 * floor):
+            worst = max(worst, (e64 / max(TOL, 2 * floor), n))
+            continue
+        if n == "pose":
+            failures.append((n, e32, e64, floor))
+            continue
+        # per-pixel gradients (disparities, masks, feature maps) are discontinuous where a bilinear tap set changes and at
+        # the |x_n| = 1 overwrite of the zeros padding; the networks' near-identity poses put whole border columns there,
+        # so a pixel may take the other side in fp32: bound the NUMBER of pixels off by more than 1e-4
+        bad = outliers(g, rr, TOL)
+        worst_px = max(worst_px, (bad / g.numel(), n))
+        if bad > 2e-4 * g.numel():
+            failures.append((n, "outliers", bad, g.numel(), e32, e64, floor))
+    if exp_masks is not None:
+        if not abs(le - r64[2]) <= 1e-5 * abs(r64[2]):
+            failures.append(("explainability", le, r64[2]))
+        for s, (g, rr) in enumerate(zip(g_exp, r64[3])):
+            if not rel_err(g, rr) < 1e-5:
+                failures.append(("explainability grad", s, rel_err(g, rr)))
+    print("cfg %d loss stage: terms vs fp64 %s; worst gradient at %.2f of its bound (%s); per-pixel outliers %.1e (%s)" %
+          (config, {k: "%.1e" % (abs(v - r64[0][k]) / abs(r64[0][k])) for k, v in terms.items()}, *worst, *worst_px))
+    assert not failures, (config, failures)
