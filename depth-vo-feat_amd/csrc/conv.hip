@@ -1019,13 +1019,6 @@ int make_dgrad_op(const dvf_conv_desc *d, const float *dpre, float *din, int off
     return op.ncls >= 1 ? DVF_OK : DVF_ERR_UNSUPPORTED;
 }
 
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
 // Forward through the unpacked kernels.  ws_need != nullptr: only report the split-K workspace the call would use.
 int fwd_unpacked(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg, const float *w,
                  const float *bias, float *out, float *ws, int64_t ws_floats, int64_t *ws_need, void *stream) {
@@ -1075,24 +1068,7 @@ int fwd_unpacked(const dvf_conv_desc *d, const float *const *in_segs, const int 
     const int ncls = scatter_classes(d->stride, d->pad, d->KH, d->KW, d->H_out, d->W_out, cls, &covers);
     return run_classes(a, cls, ncls, covers, dvf_stream(stream), ws, ws_floats, ws_need);
 }
-}  // namespace
 
-extern "C" {
-
-int dvf_conv2d_fwd_ws(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
-                      const float *w, const float *bias, float *out, float *ws, int64_t ws_floats, void *stream) {
-    dvf_plan_reset();
-    return fwd_unpacked(d, in_segs, seg_channels, nseg, w, bias, out, ws, ws_floats, nullptr, stream);
-}
-
-int dvf_conv2d_fwd(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
-                   const float *w, const float *bias, float *out, void *stream) {
-    return dvf_conv2d_fwd_ws(d, in_segs, seg_channels, nseg, w, bias, out, nullptr, 0, stream);
-}
-
-}  // extern "C"
-
-namespace {
 // dgrad of one input segment with the unpacked weights: the head kernel for narrow segments, else conv_gather_kernel
 int dgrad_segment_unpacked(const dvf_conv_desc *d, const float *dpre, const float *w, float *din, int off, int segc,
                            hipStream_t st, float *ws = nullptr, int64_t ws_floats = 0, int64_t *ws_need = nullptr,
@@ -1237,32 +1213,6 @@ int wgrad_pipe_op(const WgradArgs &o, const float *const *qsegs, const int *qseg
 
 extern "C" {
 
-int dvf_conv2d_dgrad_ws(const dvf_conv_desc *d, const float *dpre, const float *w, float *const *din_segs,
-                        const int *seg_channels, int nseg, float *ws, int64_t ws_floats, void *stream) {
-    dvf_plan_reset();
-    int rc = check_desc(d);
-    if (rc) return rc;
-    rc = check_segs(d, seg_channels, nseg);
-    if (rc) return rc;
-    if (!dpre || !w || !din_segs) return DVF_ERR_INVALID_ARG;
-    if (dvf_head_applicable(d, nseg)) return din_segs[0] ? dvf_head_dgrad(d, dpre, w, din_segs[0], dvf_stream(stream)) : DVF_OK;   // (unpacked route)
-    int off = 0;
-    for (int s = 0; s < nseg; ++s) {
-        const int segc = seg_channels[s];
-        if (din_segs[s]) {
-            rc = dgrad_segment_unpacked(d, dpre, w, din_segs[s], off, segc, dvf_stream(stream), ws, ws_floats);
-            if (rc) return rc;
-        }
-        off += segc;
-    }
-    return DVF_OK;
-}
-
-int dvf_conv2d_dgrad(const dvf_conv_desc *d, const float *dpre, const float *w, float *const *din_segs,
-                     const int *seg_channels, int nseg, void *stream) {
-    return dvf_conv2d_dgrad_ws(d, dpre, w, din_segs, seg_channels, nseg, nullptr, 0, stream);
-}
-
 static int wgrad_impl(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg, const float *dpre,
                       float *dw, int accumulate, float *dbias, bool *bias_done, void *stream, float *ws = nullptr,
                       int64_t ws_floats = 0, int64_t *ws_need = nullptr, bool plan_only = false);
@@ -1278,9 +1228,9 @@ int64_t dvf_conv2d_wgrad_ws_floats(const dvf_conv_desc *d, const int *seg_channe
     return need > nb ? need : nb;
 }
 
-int dvf_conv2d_wgrad_det(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
-                         const float *dpre, float *dw, int accumulate, float *dbias, int accumulate_dbias, float *ws,
-                         int64_t ws_floats, void *stream) {
+int dvf_conv2d_wgrad(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
+                     const float *dpre, float *dw, int accumulate, float *dbias, int accumulate_dbias, float *ws,
+                     int64_t ws_floats, void *stream) {
     if (!d) return DVF_ERR_INVALID_ARG;
     hipStream_t st = dvf_stream(stream);
     if (dbias && !accumulate_dbias &&
@@ -1289,25 +1239,8 @@ int dvf_conv2d_wgrad_det(const dvf_conv_desc *d, const float *const *in_segs, co
     bool done = false;
     const int rc = wgrad_impl(d, in_segs, seg_channels, nseg, dpre, dw, accumulate, dbias, dbias ? &done : nullptr, stream, ws, ws_floats);
     if (rc || done || !dbias) return rc;
-    return dvf_act_bwd_det(dpre, nullptr, nullptr, dbias, d->N, d->C_out, d->H_out * d->W_out, DVF_ACT_NONE, 1.f, 0.f, 1, ws, ws_floats, stream);
-}
-
-int dvf_conv2d_wgrad(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
-                     const float *dpre, float *dw, int accumulate, void *stream) {
-    return wgrad_impl(d, in_segs, seg_channels, nseg, dpre, dw, accumulate, nullptr, nullptr, stream);
-}
-
-int dvf_conv2d_wgrad_bias(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
-                          const float *dpre, float *dw, int accumulate, float *dbias, int accumulate_dbias, void *stream) {
-    if (!dbias || !d) return DVF_ERR_INVALID_ARG;
-    hipStream_t st = dvf_stream(stream);
-    if (!accumulate_dbias && hipMemsetAsync(dbias, 0, sizeof(float) * (size_t)(d->C_out > 0 ? d->C_out : 0), st) != hipSuccess)
-        return DVF_ERR_LAUNCH;
-    bool done = false;
-    const int rc = wgrad_impl(d, in_segs, seg_channels, nseg, dpre, dw, accumulate, dbias, &done, stream);
-    if (rc || done) return rc;
     // the weight-gradient launch had no spare column (or ran another kernel): one pass over dpre
-    return dvf_act_bwd2(dpre, nullptr, nullptr, dbias, d->N, d->C_out, d->H_out * d->W_out, DVF_ACT_NONE, 1.f, 0.f, 1, stream);
+    return dvf_act_bwd(dpre, nullptr, nullptr, dbias, d->N, d->C_out, d->H_out * d->W_out, DVF_ACT_NONE, 1.f, 0.f, 1, ws, ws_floats, stream);
 }
 
 static int wgrad_impl(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg, const float *dpre,
@@ -1474,27 +1407,8 @@ int64_t dvf_act_bwd_ws_floats(int N, int C, int HW) {
     return (int64_t)C * N * act_bwd_chunks(N, C, HW, true);
 }
 
-int dvf_act_bwd_det(const float *dy, const float *y, float *dpre, float *dbias, int N, int C, int HW, int act, float alpha,
-                    float beta, int accumulate_dbias, float *ws, int64_t ws_floats, void *stream) {
-    if (!dy || (act != DVF_ACT_NONE && !y) || N <= 0 || C <= 0 || HW <= 0) return DVF_ERR_INVALID_ARG;
-    if (!dbias || !ws || ws_floats < dvf_act_bwd_ws_floats(N, C, HW))
-        return dvf_act_bwd2(dy, y, dpre, dbias, N, C, HW, act, alpha, beta, accumulate_dbias, stream);
-    hipStream_t st = dvf_stream(stream);
-    if (!accumulate_dbias && hipMemsetAsync(dbias, 0, sizeof(float) * C, st) != hipSuccess) return DVF_ERR_LAUNCH;
-    const bool vec = (HW % 4 == 0) && ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(y) |
-                                        reinterpret_cast<uintptr_t>(dpre)) % 16 == 0);
-    const int chunks = act_bwd_chunks(N, C, HW, true);
-    const int64_t planes = (int64_t)N * C;
-    if (vec) act_bwd_kernel<true><<<(unsigned)(planes * chunks), 256, 0, st>>>(dy, y, dpre, dbias, C, HW, act, alpha, beta, chunks, ws, N * chunks);
-    else act_bwd_kernel<false><<<(unsigned)(planes * chunks), 256, 0, st>>>(dy, y, dpre, dbias, C, HW, act, alpha, beta, chunks, ws, N * chunks);
-    DVF_LAUNCH_CHECK();
-    bias_finish_kernel<<<C, 64, 0, st>>>(ws, dbias, N * chunks);
-    DVF_LAUNCH_CHECK();
-    return DVF_OK;
-}
-
-int dvf_act_bwd2(const float *dy, const float *y, float *dpre, float *dbias, int N, int C, int HW, int act, float alpha,
-                 float beta, int accumulate_dbias, void *stream) {
+int dvf_act_bwd(const float *dy, const float *y, float *dpre, float *dbias, int N, int C, int HW, int act, float alpha,
+                float beta, int accumulate_dbias, float *ws, int64_t ws_floats, void *stream) {
     if (!dy || (act != DVF_ACT_NONE && !y) || N <= 0 || C <= 0 || HW <= 0) return DVF_ERR_INVALID_ARG;
     if (!dpre && !dbias) return DVF_OK;
     hipStream_t st = dvf_stream(stream);
@@ -1503,15 +1417,16 @@ int dvf_act_bwd2(const float *dy, const float *y, float *dpre, float *dbias, int
                                         reinterpret_cast<uintptr_t>(dpre)) % 16 == 0);
     const int chunks = act_bwd_chunks(N, C, HW, dbias != nullptr);
     const int64_t planes = (int64_t)N * C;
-    if (vec) act_bwd_kernel<true><<<(unsigned)(planes * chunks), 256, 0, st>>>(dy, y, dpre, dbias, C, HW, act, alpha, beta, chunks);
-    else act_bwd_kernel<false><<<(unsigned)(planes * chunks), 256, 0, st>>>(dy, y, dpre, dbias, C, HW, act, alpha, beta, chunks);
+    // with the scratch: per-block partial sums, added in index order by bias_finish_kernel (else float atomics on dbias)
+    float *part = (dbias && ws && ws_floats >= dvf_act_bwd_ws_floats(N, C, HW)) ? ws : nullptr;
+    if (vec) act_bwd_kernel<true><<<(unsigned)(planes * chunks), 256, 0, st>>>(dy, y, dpre, dbias, C, HW, act, alpha, beta, chunks, part, N * chunks);
+    else act_bwd_kernel<false><<<(unsigned)(planes * chunks), 256, 0, st>>>(dy, y, dpre, dbias, C, HW, act, alpha, beta, chunks, part, N * chunks);
     DVF_LAUNCH_CHECK();
+    if (part) {
+        bias_finish_kernel<<<C, 64, 0, st>>>(part, dbias, N * chunks);
+        DVF_LAUNCH_CHECK();
+    }
     return DVF_OK;
-}
-
-int dvf_act_bwd(const float *dy, const float *y, float *dpre, float *dbias, int N, int C, int HW, int act, float alpha,
-                float beta, void *stream) {
-    return dvf_act_bwd2(dy, y, dpre, dbias, N, C, HW, act, alpha, beta, 0, stream);
 }
 
 }  // extern "C"
@@ -1600,43 +1515,48 @@ int dvf_conv2d_pack(const dvf_conv_desc *d, const int *seg_channels, int nseg, i
     return DVF_OK;
 }
 
-int dvf_conv2d_fwd_packed(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
-                          const float *packed, const float *bias, float *out, float *ws, int64_t ws_floats, void *stream) {
+int dvf_conv2d_fwd(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
+                   const float *packed, const float *w, const float *bias, float *out, float *ws, int64_t ws_floats,
+                   void *stream) {
     dvf_plan_reset();
     int rc = check_desc(d);
     if (rc) return rc;
     rc = check_segs(d, seg_channels, nseg);
     if (rc) return rc;
-    if (!in_segs || !packed || !out) return DVF_ERR_INVALID_ARG;
+    if (!in_segs || !w || !out) return DVF_ERR_INVALID_ARG;
     for (int s = 0; s < nseg; ++s)
         if (!in_segs[s]) return DVF_ERR_INVALID_ARG;
-    PipeOp op;
-    rc = make_fwd_op(d, in_segs, seg_channels, nseg, bias, out, op);
-    if (rc) return rc;
-    return pipe_run(op, packed, ws, ws_floats, dvf_stream(stream));
+    if (packed) {
+        PipeOp op;
+        rc = make_fwd_op(d, in_segs, seg_channels, nseg, bias, out, op);
+        if (!rc) rc = pipe_run(op, packed, ws, ws_floats, dvf_stream(stream));
+        // refused for this geometry, or at run time (an operand of a 16-byte-lane plan is not 16-byte aligned): the
+        // unpacked kernels take the call -- pipe_run refuses before it notes a plan or launches anything
+        if (rc != DVF_ERR_UNSUPPORTED) return rc;
+    }
+    return fwd_unpacked(d, in_segs, seg_channels, nseg, w, bias, out, ws, ws_floats, nullptr, stream);
 }
 
 // dgrad of every requested segment; packed == NULL: unpacked kernels only.  mask_segs[s] != NULL: segment s was produced
-// by a ReLU layer whose output is mask_segs[s]; its gradient leaves already multiplied by relu'() and its channel sums are
-// added to dbias_segs[s] (fused in the pipelined kernel / its split-K finish, a pass of act_bwd_kernel after the others).
-static int dgrad_all(const dvf_conv_desc *d, const float *dpre, const float *packed, const float *w, float *const *din_segs,
+// by a ReLU layer whose output is mask_segs[s]; its gradient leaves already multiplied by relu'() (in the kernel's
+// epilogue / its split-K finish, or a pass of act_bwd_kernel after it).
+int dvf_conv2d_dgrad(const dvf_conv_desc *d, const float *dpre, const float *packed, const float *w, float *const *din_segs,
                      const int *seg_channels, int nseg, float *ws, int64_t ws_floats, const float *const *mask_segs,
-                     float *const *dbias_segs, hipStream_t st) {
-    const int HWin = d->H_in * d->W_in;
-    auto postpass = [&](int s) -> int {
-        if (!mask_segs || !mask_segs[s] || !din_segs[s]) return DVF_OK;
-        return dvf_act_bwd2(din_segs[s], mask_segs[s], din_segs[s], dbias_segs ? dbias_segs[s] : nullptr, d->N, seg_channels[s],
-                            HWin, DVF_ACT_RELU, 1.f, 0.f, 1, st);
-    };
-    if (dvf_head_dgrad_applicable(d, nseg) || (dvf_head_applicable(d, nseg) && !packed)) {
-        if (!din_segs[0]) return DVF_OK;
-        if (!w) return DVF_ERR_INVALID_ARG;
-        return dvf_head_dgrad(d, dpre, w, din_segs[0], st, mask_segs ? mask_segs[0] : nullptr);     // (mask applied in the kernel)
-    }
+                     void *stream) {
+    dvf_plan_reset();
+    int rc = check_desc(d);
+    if (rc) return rc;
+    rc = check_segs(d, seg_channels, nseg);
+    if (rc) return rc;
+    if (!dpre || !w || !din_segs) return DVF_ERR_INVALID_ARG;
+    hipStream_t st = dvf_stream(stream);
+    auto mask = [&](int s) -> const float * { return mask_segs ? mask_segs[s] : nullptr; };
+    if (dvf_head_dgrad_applicable(d, nseg) || (dvf_head_applicable(d, nseg) && !packed))
+        return din_segs[0] ? dvf_head_dgrad(d, dpre, w, din_segs[0], st, mask(0)) : DVF_OK;     // (mask applied in the kernel)
     PipeOp op;
     int off = 0;
     for (int s = 0; s < nseg; ++s) {
-        int rc = DVF_ERR_UNSUPPORTED;
+        rc = DVF_ERR_UNSUPPORTED;
         int64_t nf = 0;
         if (packed) {
             rc = make_dgrad_op(d, dpre, din_segs[s], off, seg_channels[s], op);
@@ -1646,24 +1566,22 @@ static int dgrad_all(const dvf_conv_desc *d, const float *dpre, const float *pac
         }
         auto unpacked = [&]() -> int {
             if (!din_segs[s]) return DVF_OK;
-            if (!w) return DVF_ERR_INVALID_ARG;
             int done = 0;
-            int r = dgrad_segment_unpacked(d, dpre, w, din_segs[s], off, seg_channels[s], st, ws, ws_floats, nullptr,
-                                           mask_segs ? mask_segs[s] : nullptr, &done);
-            if (r) return r;
-            return done ? DVF_OK : postpass(s);
+            int r = dgrad_segment_unpacked(d, dpre, w, din_segs[s], off, seg_channels[s], st, ws, ws_floats, nullptr, mask(s), &done);
+            if (r || done || !mask(s)) return r;
+            return dvf_act_bwd(din_segs[s], mask(s), din_segs[s], nullptr, d->N, seg_channels[s], d->H_in * d->W_in, DVF_ACT_RELU,
+                               1.f, 0.f, 1, nullptr, 0, st);
         };
         if (rc == DVF_ERR_UNSUPPORTED) {                                      // narrow segment: unpacked kernels
             rc = unpacked();
             if (rc) return rc;
         } else {
             if (din_segs[s]) {
-                op.a.mask = (mask_segs && mask_segs[s]) ? mask_segs[s] : nullptr;
-                op.a.dbias = (op.a.mask && dbias_segs) ? dbias_segs[s] : nullptr;
+                op.a.mask = mask(s);
                 rc = pipe_run(op, packed, ws, ws_floats, st);
                 // refused at run time (an operand of a 16-byte-lane plan is not 16-byte aligned): this segment runs unpacked,
                 // masked or not -- the caller must not have to know which of its segments were packed
-                if (rc == DVF_ERR_UNSUPPORTED && w) rc = unpacked();
+                if (rc == DVF_ERR_UNSUPPORTED) rc = unpacked();
                 if (rc) return rc;
             }
             packed += nf;
@@ -1672,32 +1590,6 @@ static int dgrad_all(const dvf_conv_desc *d, const float *dpre, const float *pac
     }
     return DVF_OK;
 }
-
-int dvf_conv2d_dgrad_packed(const dvf_conv_desc *d, const float *dpre, const float *packed, const float *w,
-                            float *const *din_segs, const int *seg_channels, int nseg, float *ws, int64_t ws_floats,
-                            void *stream) {
-    dvf_plan_reset();
-    int rc = check_desc(d);
-    if (rc) return rc;
-    rc = check_segs(d, seg_channels, nseg);
-    if (rc) return rc;
-    if (!dpre || !packed || !din_segs) return DVF_ERR_INVALID_ARG;
-    if (dvf_head_dgrad_applicable(d, nseg)) return DVF_ERR_UNSUPPORTED;
-    return dgrad_all(d, dpre, packed, w, din_segs, seg_channels, nseg, ws, ws_floats, nullptr, nullptr, dvf_stream(stream));
-}
-
-int dvf_conv2d_dgrad_masked(const dvf_conv_desc *d, const float *dpre, const float *packed, const float *w,
-                            float *const *din_segs, const int *seg_channels, int nseg, float *ws, int64_t ws_floats,
-                            const float *const *mask_segs, float *const *dbias_segs, void *stream) {
-    dvf_plan_reset();
-    int rc = check_desc(d);
-    if (rc) return rc;
-    rc = check_segs(d, seg_channels, nseg);
-    if (rc) return rc;
-    if (!dpre || !din_segs || !mask_segs || (!packed && !w)) return DVF_ERR_INVALID_ARG;
-    return dgrad_all(d, dpre, packed, w, din_segs, seg_channels, nseg, ws, ws_floats, mask_segs, dbias_segs, dvf_stream(stream));
-}
-
 
 // ---- batched packing: every convolution's job in one launch per optimizer step
 int dvf_conv2d_pack_jobs(const dvf_conv_desc *d, const int *seg_channels, int nseg, int op_kind, const float *w, float *packed,

@@ -78,10 +78,9 @@ struct PipeArgs {
     int SLmax, PSRmax, NST;               // LDS carve per stage (NST = 2 or 3 stages): SLmax weight floats | CK * PSRmax patch floats
     int dbg;                              // ablation switches (tools/conv_bench.py): 1 no patch loads, 2 no weight loads, 4 no MFMA
     unsigned long long *stamps;           // -DDVF_TUNING builds: per-block cycle account (8 x u64 per block), or NULL
-    // dgrad of a segment produced by a ReLU layer (out_mode 0): out = (mask > 0) ? v : 0 and dbias[channel] += sum(out) --
-    // the activation backward pass and the bias gradient of the PRODUCING layer, done where its gradient is born
+    // dgrad of a segment produced by a ReLU layer (out_mode 0): out = (mask > 0) ? v : 0 -- the activation backward pass
+    // of the PRODUCING layer, done where its gradient is born
     const float *mask;                    // same shape as out (the producing layer's output), or NULL
-    float *dbias;                         // [M] accumulated with float atomics, or NULL
 };
 
 __host__ __device__ inline int pipe_row_stride(int RSu, int SW, int SH, int IS) {
@@ -587,12 +586,7 @@ __global__ __launch_bounds__(PIPE_THREADS_4P) void conv_pipe_kernel(const PipeAr
     float *outp = a.out + (a.out_mode == 2 ? (int64_t)ks * a.ws_slice : 0);
     const int64_t HW = (int64_t)a.OH * a.OW;
     if (a.mask && a.out_mode == 0) {
-        // ReLU backward of the producing layer + its bias gradient (no bias / activation of this op: it is a dgrad)
-        float csum[MT][16];
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) csum[m][r] = 0.f;
+        // ReLU backward of the producing layer (no bias / activation of this op: it is a dgrad)
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
             const int oy = oy0 + opy[i], ox = ox0 + opx[i], n = n0 + opn[i];
@@ -615,24 +609,10 @@ __global__ __launch_bounds__(PIPE_THREADS_4P) void conv_pipe_kernel(const PipeAr
                 for (int r = 0; r < 16; ++r) {
                     const int ml = m * 32 + (r & 3) + 8 * (r >> 2);
                     if (pok && m0 + 4 * kh + ml < a.M) {
-                        const float v = mk[m][r] > 0.f ? acc[m][i][r] : 0.f;
-                        outp[base + (int64_t)ml * HW] = v;
-                        csum[m][r] += v;
+                        outp[base + (int64_t)ml * HW] = mk[m][r] > 0.f ? acc[m][i][r] : 0.f;
                     }
                 }
             }
-        }
-        if (a.dbias) {
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float sv = csum[m][r];
-#pragma unroll
-                    for (int off = 16; off > 0; off >>= 1) sv += __shfl_xor(sv, off, 64);   // over the 32 pixels of this half-wave
-                    const int mm = m0 + 4 * kh + m * 32 + (r & 3) + 8 * (r >> 2);
-                    if (nl == 0 && mm < a.M) atomicAdd(a.dbias + mm, sv);
-                }
         }
         stamp_out();
         return;

@@ -168,39 +168,30 @@ __global__ void splitk_reduce_kernel(const float *ws, float *out, const float *b
     }
 }
 
-// Split-K finish of a dgrad whose segment was produced by a ReLU layer: out = (mask > 0) ? sum_k ws[k] : 0 and
-// dbias[c] += sum(out).  One block per chunk of one (n, c) plane: fixed-order sum of the partial tiles, one atomic per block.
-__global__ __launch_bounds__(256) void splitk_reduce_mask_kernel(const float *ws, float *out, const float *mask, float *dbias,
-                                                                 int KS, int64_t slice, int C, int HW, int chunks) {
-    __shared__ float red[4];
+// Split-K finish of a dgrad whose segment was produced by a ReLU layer: out = (mask > 0) ? sum_k ws[k] : 0.  One block per
+// chunk of one (n, c) plane: fixed-order sum of the partial tiles.
+__global__ __launch_bounds__(256) void splitk_reduce_mask_kernel(const float *ws, float *out, const float *mask, int KS,
+                                                                 int64_t slice, int HW, int chunks) {
     const int plane = blockIdx.x / chunks, chunk = blockIdx.x - plane * chunks;
     const int per = (HW + chunks - 1) / chunks;
     const int lo = chunk * per, hi = min(HW, lo + per);
     const int64_t base = (int64_t)plane * HW;
-    float s = 0.f;
     for (int e = lo + threadIdx.x; e < hi; e += 256) {
         const int64_t i = base + e;
         float v = ws[i];
         for (int k = 1; k < KS; ++k) v += ws[i + k * slice];
-        v = mask[i] > 0.f ? v : 0.f;
-        out[i] = v;
-        s += v;
+        out[i] = mask[i] > 0.f ? v : 0.f;
     }
-    if (!dbias) return;
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(dbias + plane % C, red[0] + red[1] + red[2] + red[3]);
 }
 
 // KS >= 8 (the 2x7 ... 8x26 layers: 8-64 partial tiles of a few thousand elements each): the k range is split over the four
 // waves of a block -- each wave sums a contiguous quarter of the partial tiles in order, the quarters are added in order (a
 // fixed tree: deterministic) -- and a block takes 64 consecutive elements, so the reduce of a 28 672-element output with
 // KS = 64 is 448 blocks x 16 independent loads per thread instead of 112 blocks x 64 (round 3: 20 us -> the launch floor).
-// mask != NULL: the dgrad finish of splitk_reduce_mask_kernel (out = mask > 0 ? sum : 0, dbias[c] += plane sums).
+// mask != NULL: the dgrad finish of splitk_reduce_mask_kernel (out = mask > 0 ? sum : 0).
 __global__ __launch_bounds__(256) void splitk_reduce_kpar_kernel(const float *ws, float *out, const float *bias, const float *mask,
-                                                                 float *dbias, int KS, int64_t slice, int C, int HW, int act,
-                                                                 float alpha, float beta) {
+                                                                 int KS, int64_t slice, int C, int HW, int act, float alpha,
+                                                                 float beta) {
     __shared__ float part[3][64];
     const int lane = threadIdx.x & 63, kq = threadIdx.x >> 6;
     const int k0 = (KS * kq) >> 2, k1 = (KS * (kq + 1)) >> 2;
@@ -214,25 +205,14 @@ __global__ __launch_bounds__(256) void splitk_reduce_kpar_kernel(const float *ws
     if (kq) part[kq - 1][lane] = v;
     __syncthreads();
     if (kq) return;
-    const bool ok = i < slice;
+    if (i >= slice) return;
     v = ((v + part[0][lane]) + part[1][lane]) + part[2][lane];
-    const int64_t plane = ok ? i / HW : -1;
-    if (!mask) {
-        if (ok) {
-            if (bias) v += bias[(int)(plane % C)];
-            out[i] = dvfp::apply_act(v, act, alpha, beta);
-        }
+    if (mask) {
+        out[i] = mask[i] > 0.f ? v : 0.f;
         return;
     }
-    v = (ok && mask[i] > 0.f) ? v : 0.f;
-    if (ok) out[i] = v;
-    if (!dbias) return;
-    // the 64 elements of this wave span a few (n, c) planes: one atomic per plane
-    const int64_t ilast = (i0 + 63 < slice ? i0 + 63 : slice - 1);
-    for (int64_t pl = i0 / HW; pl <= ilast / HW; ++pl) {
-        const float s = wave_sum(plane == pl ? v : 0.f);
-        if (lane == 0) atomicAdd(dbias + (int)(pl % C), s);
-    }
+    if (bias) v += bias[(int)((i / HW) % C)];
+    out[i] = dvfp::apply_act(v, act, alpha, beta);
 }
 
 #ifdef DVF_TUNING
@@ -525,14 +505,14 @@ int pipe_run(PipeOp &op, const float *packed, float *ws, int64_t ws_floats, hipS
     if (rc) return rc;
     const int64_t nb = (total + 255) / 256;
     if (mode == 2 && a.KS >= 8 && HW < ((int64_t)1 << 30)) {
-        splitk_reduce_kpar_kernel<<<(unsigned)((total + 63) / 64), 256, 0, st>>>(ws, out, a.bias, a.mask, a.dbias, a.KS, total, a.M,
-                                                                                (int)HW, a.act, a.alpha, a.beta);
+        splitk_reduce_kpar_kernel<<<(unsigned)((total + 63) / 64), 256, 0, st>>>(ws, out, a.bias, a.mask, a.KS, total, a.M, (int)HW,
+                                                                                a.act, a.alpha, a.beta);
         DVF_LAUNCH_CHECK();
     } else if (mode == 2 && a.mask) {
         int chunks = 1;
         const int64_t planes = (int64_t)a.N * a.M;
         while (planes * chunks < 1024 && HW / (chunks * 2) >= 256) chunks *= 2;
-        splitk_reduce_mask_kernel<<<(unsigned)(planes * chunks), 256, 0, st>>>(ws, out, a.mask, a.dbias, a.KS, total, a.M, (int)HW, chunks);
+        splitk_reduce_mask_kernel<<<(unsigned)(planes * chunks), 256, 0, st>>>(ws, out, a.mask, a.KS, total, (int)HW, chunks);
         DVF_LAUNCH_CHECK();
     } else if (mode == 2) {
         splitk_reduce_kernel<<<(int)(nb > 4096 ? 4096 : nb), 256, 0, st>>>(ws, out, a.bias, a.KS, total, a.M, HW, a.act,
@@ -543,7 +523,7 @@ int pipe_run(PipeOp &op, const float *packed, float *ws, int64_t ws_floats, hipS
         DVF_LAUNCH_CHECK();
     }
     if (mode == 1 && a.mask)    // atomic accumulation into a zeroed output: the mask pass runs over the finished sums
-        return dvf_act_bwd2(out, a.mask, out, a.dbias, a.N, a.M, (int)HW, DVF_ACT_RELU, 1.f, 0.f, 1, st);
+        return dvf_act_bwd(out, a.mask, out, nullptr, a.N, a.M, (int)HW, DVF_ACT_RELU, 1.f, 0.f, 1, nullptr, 0, st);
     return DVF_OK;
 }
 

@@ -8,7 +8,7 @@ DvfPlanLog &dvf_plan_log() {
 
 extern "C" {
 
-int dvf_version(void) { return 200; }
+int dvf_version(void) { return 300; }
 
 int dvf_conv2d_last_plans(int *out, int max_ints) {
     if (!out || max_ints < 0) return DVF_ERR_INVALID_ARG;

@@ -24,7 +24,6 @@ class _NullCtx:
 
 
 _NULL = _NullCtx()
-_NULL_PTRS = [(ctypes.c_void_p * max(n, 1))() for n in range(9)]    # all-NULL pointer tables by length
 
 
 def conv_out_size(h, k, stride, pad, opad, transposed):
@@ -183,14 +182,10 @@ def set_deterministic(on=True):
 
 
 def _bias_sums(lib, dy, y, dpre, dbias, N, C, HW, act, alpha, beta, accumulate):
-    """dvf_act_bwd2 (dpre = dy * act'(y), dbias (+)= channel sums), through the deterministic entry when asked."""
-    if DETERMINISTIC and dbias is not None:
-        ws = _workspace(int(lib.dvf_act_bwd_ws_floats(N, C, HW)), dy.device)
-        L.check(lib.dvf_act_bwd_det(L.dev(dy, "grad_out"), L.dev(y), L.dev(dpre), L.dev(dbias), N, C, HW, act, alpha, beta,
-                                    1 if accumulate else 0, L.dev(ws), ws.numel(), L.stream()), "dvf_act_bwd_det")
-    else:
-        L.check(lib.dvf_act_bwd2(L.dev(dy, "grad_out"), L.dev(y), L.dev(dpre), L.dev(dbias), N, C, HW, act, alpha, beta,
-                                 1 if accumulate else 0, L.stream()), "dvf_act_bwd2")
+    """dvf_act_bwd (dpre = dy * act'(y), dbias (+)= channel sums), summed in a fixed order through a scratch when asked."""
+    ws = _workspace(int(lib.dvf_act_bwd_ws_floats(N, C, HW)), dy.device) if (DETERMINISTIC and dbias is not None) else None
+    L.check(lib.dvf_act_bwd(L.dev(dy, "grad_out"), L.dev(y), L.dev(dpre), L.dev(dbias), N, C, HW, act, alpha, beta,
+                            1 if accumulate else 0, L.dev(ws), ws.numel() if ws is not None else 0, L.stream()), "dvf_act_bwd")
 
 
 def _wgrad_ws_floats(holder, desc, segc):
@@ -205,13 +200,13 @@ def _wgrad_ws_floats(holder, desc, segc):
 
 
 GEOM_LOG = None   # set to a list(): ConvFn.forward appends the geometry of every call (tests: bench-shape parity)
-FUSE_RELU_BWD = True   # False: every layer runs its own activation backward pass (dvf_act_bwd2), as in round 1
+FUSE_RELU_BWD = True   # False: every layer runs its own activation backward pass (dvf_act_bwd), as in round 1
 
 
 class ReluTag:
     """Carried by the output y of a ReLU convolution whose module was declared ``fuse_bwd`` (EVERY consumer of y is a
     ConvFn): the consumers' dgrad kernels then deliver dL/dy already multiplied by relu'(y) -- the producing layer runs no
-    activation backward pass, and its bias gradient is one more column of its weight-gradient GEMM (dvf_conv2d_wgrad_bias).  relu' is a 0/1
+    activation backward pass, and its bias gradient is one more column of its weight-gradient GEMM (dvf_conv2d_wgrad).  relu' is a 0/1
     mask, so masking each consumer's contribution equals masking their sum."""
     __slots__ = ()
 
@@ -289,17 +284,11 @@ class ConvFn(torch.autograd.Function):
         bp = bias.data_ptr() if bias is not None else None
         lib = L.lib()
         with (L.timed("conv_fwd", 2 * g.macs, tag=g.tag) if L.TIMER is not None else _NULL):
-            rc = L.ERR_UNSUPPORTED
-            if packed is not None:
-                rc = lib.dvf_conv2d_fwd_packed(g.dref, inarr, g.segarr, g.nseg, packed.data_ptr(), bp, out.data_ptr(),
-                                               wsp, wsn, L.stream_raw())
-                if rc != 0 and rc != L.ERR_UNSUPPORTED:     # (unsupported at run time: an operand is not 16-byte aligned)
-                    L.check(rc, "dvf_conv2d_fwd_packed")
-            if rc == L.ERR_UNSUPPORTED:
-                rc = lib.dvf_conv2d_fwd_ws(g.dref, inarr, g.segarr, g.nseg, weight.data_ptr(), bp, out.data_ptr(), wsp, wsn,
-                                           L.stream_raw())
-                if rc != 0:
-                    L.check(rc, "dvf_conv2d_fwd_ws")
+            # (the library runs the unpacked kernels when the packed plan is refused, e.g. for an unaligned operand)
+            rc = lib.dvf_conv2d_fwd(g.dref, inarr, g.segarr, g.nseg, packed.data_ptr() if packed is not None else None,
+                                    weight.data_ptr(), bp, out.data_ptr(), wsp, wsn, L.stream_raw())
+            if rc != 0:
+                L.check(rc, "dvf_conv2d_fwd")
         if L.PLAN_LOG is not None:
             L.note_plans("fwd")
         ctx.save_for_backward(weight, out, *inputs)
@@ -347,25 +336,13 @@ class ConvFn(torch.autograd.Function):
             masked = [t is not None and need for t, need in zip(ctx.in_tags, need_in)]
             if timing:
                 frac = sum(c for c, need in zip(segc, need_in) if need) / float(sum(segc))
+            marr = None
+            if True in masked:      # segments produced by fuse_bwd ReLU layers: their gradient leaves masked by relu'(y)
+                marr = (ctypes.c_void_p * g.nseg)(*[x.data_ptr() if m else None for x, m in zip(inputs, masked)])
             with (L.timed("conv_dgrad", 2 * g.macs * frac, tag=g.tag) if timing else _NULL):
-                if True in masked:
-                    # segments produced by fuse_bwd ReLU layers: their gradient leaves masked, their bias gradient summed
-                    # (a segment whose packed plan is refused at run time runs unpacked inside the library)
-                    marr = (ctypes.c_void_p * g.nseg)(*[x.data_ptr() if m else None for x, m in zip(inputs, masked)])
-                    rc = lib.dvf_conv2d_dgrad_masked(g.dref, dprep, pp, weight.data_ptr(), ginarr, g.segarr, g.nseg, wsp, wsn,
-                                                     marr, _NULL_PTRS[g.nseg], st)
-                    if rc != 0:
-                        L.check(rc, "dvf_conv2d_dgrad_masked")
-                else:
-                    rc = L.ERR_UNSUPPORTED
-                    if packed is not None:
-                        rc = lib.dvf_conv2d_dgrad_packed(g.dref, dprep, pp, weight.data_ptr(), ginarr, g.segarr, g.nseg, wsp, wsn, st)
-                        if rc != 0 and rc != L.ERR_UNSUPPORTED:
-                            L.check(rc, "dvf_conv2d_dgrad_packed")
-                    if rc == L.ERR_UNSUPPORTED:
-                        rc = lib.dvf_conv2d_dgrad_ws(g.dref, dprep, weight.data_ptr(), ginarr, g.segarr, g.nseg, wsp, wsn, st)
-                        if rc != 0:
-                            L.check(rc, "dvf_conv2d_dgrad_ws")
+                rc = lib.dvf_conv2d_dgrad(g.dref, dprep, pp, weight.data_ptr(), ginarr, g.segarr, g.nseg, wsp, wsn, marr, st)
+                if rc != 0:
+                    L.check(rc, "dvf_conv2d_dgrad")
             if L.PLAN_LOG is not None:
                 L.note_plans("dgrad")
         dw = None
@@ -384,12 +361,12 @@ class ConvFn(torch.autograd.Function):
                     # (DETERMINISTIC: partial tiles through a per-stream scratch, summed in fixed order; else float atomics)
                     wsf = _wgrad_ws_floats(ctx.wparam if arena else weight, desc, segc) if DETERMINISTIC else 0
                     wws = _workspace(wsf, dpre.device, wst, side) if wsf > 0 else None
-                    rc = lib.dvf_conv2d_wgrad_det(g.dref, ctx.inarr, g.segarr, g.nseg, dprep, dw.data_ptr(), 1 if arena else 0,
-                                                  dbias.data_ptr() if (fused_out and need_b) else None, 1 if acc_b else 0,
-                                                  wws.data_ptr() if wws is not None else None,
-                                                  wws.numel() if wws is not None else 0, wst)
+                    rc = lib.dvf_conv2d_wgrad(g.dref, ctx.inarr, g.segarr, g.nseg, dprep, dw.data_ptr(), 1 if arena else 0,
+                                              dbias.data_ptr() if (fused_out and need_b) else None, 1 if acc_b else 0,
+                                              wws.data_ptr() if wws is not None else None,
+                                              wws.numel() if wws is not None else 0, wst)
                     if rc != 0:
-                        L.check(rc, "dvf_conv2d_wgrad_det")
+                        L.check(rc, "dvf_conv2d_wgrad")
                     if L.PLAN_LOG is not None:
                         L.note_plans("wgrad")
             if arena:

@@ -60,7 +60,9 @@ int dvf_build_has_tuning(void);
 /* Which kernels the LAST dvf_conv2d_* call of this thread launched: records of 12 ints
  *   {kernel, MT, NT, WM, CK, TBU, KS, BN, NST, threads, lds_bytes, mode}   (kernel: 1 conv_pipe, 2 conv_gather,
  *   3 head_fwd {C_out, nseg}, 4 head_dgrad, 5 head_wgrad, 6 conv_wgrad {MT, NTW, prefetch, CK, BH, PSPLIT, vec_p, stride,
- *   threads, lds, KH*KW}, 7 head_seg_dgrad) copied to the HOST array `out`; returns the number of ints written.
+ *   threads, lds, KH*KW}, 7 head_seg_dgrad, 8 wgrad_pipe {MT | TILE << 8, NTW, x4 | ordered << 1, CK, stride, pieces,
+ *   blocks, lds, KH*KW, row stride, nseg}, 9 dconvt_fwd {C_out, KH}) copied to the HOST array `out`; returns the number of
+ *   ints written.
  * The planner is shape dependent; tests use this to show that every plan of the benchmark step is parity-tested. */
 int dvf_conv2d_last_plans(int *out, int max_ints);
 
@@ -176,64 +178,46 @@ typedef struct dvf_conv_desc {
 } dvf_conv_desc;
 
 /* out = act(conv(cat(in_segs), w) + bias).  Replaces nn.Conv2d / nn.ConvTranspose2d (+ReLU / Sigmoid, and the
- * alpha*sigmoid+beta of DispNetS.py:112) forward.  bias may be NULL. */
+ * alpha*sigmoid+beta of DispNetS.py:112) forward.  bias may be NULL; w may not.  packed (may be NULL): the op_kind 0
+ * copy of w (below).  The pipelined kernel reads it when its plan accepts the call; otherwise -- refused for the geometry,
+ * or at run time for an operand of a 16-byte-lane plan that is not 16-byte aligned -- the unpacked kernels read w. */
 int dvf_conv2d_fwd(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
-                   const float *w, const float *bias, float *out, void *stream);
-/* d(loss)/d(input segment i) for i with din_segs[i] != NULL, given dpre = d(loss)/d(pre-activation output). */
-int dvf_conv2d_dgrad(const dvf_conv_desc *d, const float *dpre, const float *w, float *const *din_segs,
-                     const int *seg_channels, int nseg, void *stream);
-/* d(loss)/d(w) in w's own layout; accumulate != 0 adds to dw, otherwise dw is zeroed first. */
-int dvf_conv2d_wgrad(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
-                     const float *dpre, float *dw, int accumulate, void *stream);
-/* dvf_conv2d_wgrad + the bias gradient of the same layer, dbias[c] (+)= sum over (n, y, x) of dpre[n][c][y][x]
- * (torch: the bias output of ConvolutionBackward).  For Conv2d layers the pipelined weight-gradient kernel multiplies its
- * dpre tile by one more column -- of ones -- so no extra pass reads dpre; otherwise one reduction pass runs after it. */
-int dvf_conv2d_wgrad_bias(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
-                          const float *dpre, float *dw, int accumulate, float *dbias, int accumulate_dbias, void *stream);
-/* Run-to-run DETERMINISTIC weight (+ bias, dbias may be NULL) gradient -- the reference's CPU path is (torch CPU
- * ConvolutionBackward, train.py:213).  The pipelined kernel splits the pixel reduction over all CUs; with a scratch buffer of
- * dvf_conv2d_wgrad_ws_floats(...) floats every block stores its partial tiles and one pass adds them in block order, instead
- * of float atomics in order of arrival (ws == NULL or too small: the atomic form of dvf_conv2d_wgrad / _wgrad_bias). */
+                   const float *packed, const float *w, const float *bias, float *out, float *ws, int64_t ws_floats,
+                   void *stream);
+/* d(loss)/d(input segment i) for i with din_segs[i] != NULL, given dpre = d(loss)/d(pre-activation output).  packed (may be
+ * NULL): the op_kind 1 copy of w; input segments it has no share of (at most 32 channels) and segments whose plan is refused
+ * at run time are computed from w.  mask_segs (may be NULL, and so may its entries): mask_segs[s] != NULL says input segment
+ * s is the output y of a ReLU convolution (reference: nn.ReLU(inplace=True) after every conv, DispNetS.py:10-16,30-41,
+ * PoseExpNet_sfm.py:9-13): din_segs[s] leaves as (y > 0) ? din : 0 -- which is dL/dpre of that layer when every consumer
+ * of y does the same (the ReLU mask distributes over the sum autograd forms).  Replaces torch's ThresholdBackward. */
+int dvf_conv2d_dgrad(const dvf_conv_desc *d, const float *dpre, const float *packed, const float *w, float *const *din_segs,
+                     const int *seg_channels, int nseg, float *ws, int64_t ws_floats, const float *const *mask_segs,
+                     void *stream);
+/* d(loss)/d(w) in w's own layout; accumulate != 0 adds to dw, otherwise dw is zeroed first.  dbias (may be NULL): the bias
+ * gradient of the same layer, dbias[c] (+)= sum over (n, y, x) of dpre[n][c][y][x] (torch: the bias output of
+ * ConvolutionBackward).  For Conv2d layers the pipelined weight-gradient kernel multiplies its dpre tile by one more
+ * column -- of ones -- so no extra pass reads dpre; otherwise one reduction pass runs after it.
+ * ws (may be NULL): with dvf_conv2d_wgrad_ws_floats(...) floats both gradients are run-to-run DETERMINISTIC -- the
+ * reference's CPU path is (torch CPU ConvolutionBackward, train.py:213): the pipelined kernel splits the pixel reduction over
+ * all CUs, every block stores its partial tiles and one pass adds them in block order, instead of float atomics in order
+ * of arrival (ws == NULL or too small). */
 int64_t dvf_conv2d_wgrad_ws_floats(const dvf_conv_desc *d, const int *seg_channels, int nseg);
-int dvf_conv2d_wgrad_det(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
-                         const float *dpre, float *dw, int accumulate, float *dbias, int accumulate_dbias, float *ws,
-                         int64_t ws_floats, void *stream);
+int dvf_conv2d_wgrad(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
+                     const float *dpre, float *dw, int accumulate, float *dbias, int accumulate_dbias, float *ws,
+                     int64_t ws_floats, void *stream);
 
-/* Packed-weight fast path: LDS-DMA pipelined kernels that read the weights from a pre-packed copy (the exact LDS
- * image of every reduction chunk), same results as dvf_conv2d_fwd / dvf_conv2d_dgrad.  op_kind 0 = forward,
- * 1 = dgrad.  Protocol: n = dvf_conv2d_packed_floats(...) (negative = DVF_ERR_*; DVF_ERR_UNSUPPORTED means "use the
- * unpacked entry for this geometry"); the caller allocates n floats and ZERO-FILLS them once; dvf_conv2d_pack()
- * refreshes the copy whenever w changed (after every optimizer step, train.py:214); the *_packed entries consume it.
- * The packing depends on the whole descriptor (incl. N, H, W) and on seg_channels: use the same ones everywhere. */
+/* Packed weights for the LDS-DMA pipelined kernel: the exact LDS image of every reduction chunk.  op_kind 0 = forward,
+ * 1 = dgrad.  Protocol: n = dvf_conv2d_packed_floats(...) (negative = DVF_ERR_*; DVF_ERR_UNSUPPORTED means "no packed copy
+ * for this geometry": pass packed = NULL); the caller allocates n floats and ZERO-FILLS them once; dvf_conv2d_pack()
+ * refreshes the copy whenever w changed (after every optimizer step, train.py:214).  The packing depends on the whole
+ * descriptor (incl. N, H, W) and on seg_channels: use the same ones everywhere. */
 int64_t dvf_conv2d_packed_floats(const dvf_conv_desc *d, const int *seg_channels, int nseg, int op_kind);
 int dvf_conv2d_pack(const dvf_conv_desc *d, const int *seg_channels, int nseg, int op_kind, const float *w, float *packed,
                     void *stream);
-int dvf_conv2d_fwd_packed(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
-                          const float *packed, const float *bias, float *out, float *ws, int64_t ws_floats, void *stream);
-/* (dgrad: input segments the pipelined kernel does not take -- at most 32 channels -- have no share in the packed copy
- * and are computed from the unpacked weights w, which may be NULL only if every segment is packed) */
-int dvf_conv2d_dgrad_packed(const dvf_conv_desc *d, const float *dpre, const float *packed, const float *w,
-                            float *const *din_segs, const int *seg_channels, int nseg, float *ws, int64_t ws_floats,
-                            void *stream);
-/* dgrad that also finishes the PRODUCING layers' backward pass.  mask_segs[s] != NULL says input segment s is the output
- * y of a ReLU convolution (reference: nn.ReLU(inplace=True) after every conv, DispNetS.py:10-16,30-41, PoseExpNet_sfm.py:9-13):
- * din_segs[s] leaves as (y > 0) ? din : 0 -- which is dL/dpre of that layer when every consumer of y does the same
- * (the ReLU mask distributes over the sum autograd forms) -- and its sums over (n, y, x) are ADDED to dbias_segs[s][c]
- * (that layer's bias gradient; float atomics; may be NULL).  packed may be NULL (unpacked kernels only); mask_segs entries
- * may be NULL (plain dgrad of that segment).  Replaces torch's ThresholdBackward + the bias reduction of ConvolutionBackward. */
-int dvf_conv2d_dgrad_masked(const dvf_conv_desc *d, const float *dpre, const float *packed, const float *w,
-                            float *const *din_segs, const int *seg_channels, int nseg, float *ws, int64_t ws_floats,
-                            const float *const *mask_segs, float *const *dbias_segs, void *stream);
-/* The unpacked entries with a split-K workspace (>= dvf_conv2d_ws_floats(...) floats; NULL = the float-atomic fallback of
- * dvf_conv2d_fwd / dvf_conv2d_dgrad): small grids split the reduction over blocks, and with the workspace the partial
- * tiles are summed in a fixed order -- activations are then bit-reproducible from run to run. */
-int dvf_conv2d_fwd_ws(const dvf_conv_desc *d, const float *const *in_segs, const int *seg_channels, int nseg,
-                      const float *w, const float *bias, float *out, float *ws, int64_t ws_floats, void *stream);
-int dvf_conv2d_dgrad_ws(const dvf_conv_desc *d, const float *dpre, const float *w, float *const *din_segs,
-                        const int *seg_channels, int nseg, float *ws, int64_t ws_floats, void *stream);
-/* Optional split-K workspace of the packed entries: with ws (>= dvf_conv2d_ws_floats(...) floats, contents
- * irrelevant) small grids split the reduction over blocks that store plain partial tiles which one pass reduces
- * (+bias, activation); with ws == NULL they accumulate with float atomics into a zeroed output instead. */
+/* Optional split-K workspace of dvf_conv2d_fwd (op_kind 0) and dvf_conv2d_dgrad (1): with ws (>= dvf_conv2d_ws_floats(...)
+ * floats, contents irrelevant) small grids split the reduction over blocks that store plain partial tiles which one pass
+ * sums in a fixed order (+bias, activation) -- activations are then bit-reproducible from run to run; with ws == NULL they
+ * accumulate with float atomics into a zeroed output instead. */
 int64_t dvf_conv2d_ws_floats(const dvf_conv_desc *d, const int *seg_channels, int nseg, int op_kind);
 /* Batched packing (one launch per optimizer step instead of one per convolution): dvf_conv2d_pack_jobs() writes the
  * job records of one convolution (1 for op_kind 0, nseg for op_kind 1; DVF_PACK_JOB_BYTES each, opaque) into HOST
@@ -248,18 +232,13 @@ int dvf_conv2d_pack_jobs(const dvf_conv_desc *d, const int *seg_channels, int ns
 int dvf_conv2d_pack_batch(const void *jobs_dev, const int *block_prefix_dev, const int *block_job_dev, int njobs,
                           int total_blocks, int lds_bytes, void *stream);
 /* Backward of the fused activation and of the bias in one pass: dpre = dy * act'(y) (y = the forward's
- * output, [N,C,HW]); dbias[c] = sum dpre (zeroed by the call).  dpre or dbias may be NULL. */
-int dvf_act_bwd(const float *dy, const float *y, float *dpre, float *dbias, int N, int C, int HW, int act,
-                float alpha, float beta, void *stream);
-/* Same, with accumulate_dbias != 0: dbias is NOT zeroed first, the channel sums are added to it (a bias gradient that
- * lives in a zeroed gradient arena needs neither a memset nor a separate add). */
-int dvf_act_bwd2(const float *dy, const float *y, float *dpre, float *dbias, int N, int C, int HW, int act, float alpha,
-                 float beta, int accumulate_dbias, void *stream);
-/* dvf_act_bwd2 with a run-to-run deterministic bias gradient: per-block partial sums go through ws
- * (>= dvf_act_bwd_ws_floats(N, C, HW) floats) and are added in index order instead of float atomics on dbias[c]. */
+ * output, [N,C,HW]); dbias[c] (+)= sum dpre (accumulate_dbias != 0 adds to dbias, otherwise it is zeroed first: a bias
+ * gradient that lives in a zeroed gradient arena needs neither a memset nor a separate add).  dpre or dbias may be NULL.
+ * ws (may be NULL): with dvf_act_bwd_ws_floats(N, C, HW) floats the bias gradient is run-to-run deterministic -- per-block
+ * partial sums go through ws and are added in index order instead of float atomics on dbias[c]. */
 int64_t dvf_act_bwd_ws_floats(int N, int C, int HW);
-int dvf_act_bwd_det(const float *dy, const float *y, float *dpre, float *dbias, int N, int C, int HW, int act, float alpha,
-                    float beta, int accumulate_dbias, float *ws, int64_t ws_floats, void *stream);
+int dvf_act_bwd(const float *dy, const float *y, float *dpre, float *dbias, int N, int C, int HW, int act, float alpha,
+                float beta, int accumulate_dbias, float *ws, int64_t ws_floats, void *stream);
 
 /* ---------------------------------------------------------------- memory-bound helpers
  * planes = N*C throughout. */

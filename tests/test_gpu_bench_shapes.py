@@ -164,7 +164,7 @@ def _check_geometry(gi, geom, failures):
     del rx, rw, rb, ref, pre, gout
     # ---- the same geometry as the step runs it (dvf/conv.py::ReluTag): inputs are outputs of ReLU layers, so the
     # dgrad leaves multiplied by (x > 0); a ReLU layer itself receives dL/dpre (its consumers masked it) and its
-    # bias gradient is the extra column of the weight-gradient kernel (dvf_conv2d_wgrad_bias)
+    # bias gradient is the extra column of the weight-gradient kernel (dvf_conv2d_wgrad)
     xs2 = [F.relu(x) for x in xs]
     rx = [x.clone().requires_grad_(ng) for x, ng in zip(xs2, need_in)]
     rw, rb = wt.clone().requires_grad_(True), b.clone().requires_grad_(True)

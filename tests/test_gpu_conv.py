@@ -26,6 +26,9 @@ def _ref_act(x, act, alpha, beta):
 CASES = [
     # name, segs, cout, k, stride, pad, opad, transposed, act, (N,H,W), out_hw
     ("c3x3_s1_relu", [16], 32, 3, 1, 1, 0, False, 1, (2, 20, 36), None),
+    # the same layer (conv_pipe with 16-byte lanes) also on an input at a one-float storage offset: the library refuses the
+    # pipelined plan at run time and runs the unpacked kernels
+    ("c3x3_s1_relu_offset", [16], 32, 3, 1, 1, 0, False, 1, (2, 20, 36), None),
     ("c3x3_s2_relu", [16], 64, 3, 2, 1, 0, False, 1, (2, 21, 37), None),
     ("c7x7_s2_cin3", [3], 32, 7, 2, 3, 0, False, 1, (2, 32, 48), None),
     ("c7x7_s1", [32], 32, 7, 1, 3, 0, False, 1, (1, 24, 40), None),
@@ -64,6 +67,7 @@ CASES = [
 
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_conv_fwd_bwd(case):
+    from dvf import lib as L
     from dvf.conv import ConvFn
     name, segs, cout, k, stride, pad, opad, transposed, act, (n, h, w), out_hw = case
     gen = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 10000)
@@ -90,17 +94,29 @@ def test_conv_fwd_bwd(case):
         # correct fp32 implementations (different summation order); such elements get no upstream gradient
         gout = gout * (pre.detach().abs() > 1e-4)
     (ref * gout).sum().backward()
-    # ---- HIP
-    gx = [x.clone().to(DEV).requires_grad_(True) for x in xs]
-    gw, gb = wt.clone().to(DEV).requires_grad_(True), b.clone().to(DEV).requires_grad_(True)
-    out = ConvFn.apply(gw, gb, (k, stride, pad, opad, transposed, act, alpha, beta, out_hw), *gx)
-    assert out.shape == ref.shape
-    (out * gout.to(DEV)).sum().backward()
-    assert rel_err(out, ref) < TOL, "forward"
-    assert rel_err(gw.grad, rw.grad) < TOL, "wgrad"
-    assert rel_err(gb.grad, rb.grad) < TOL, "bias grad"
-    for i, (a, r) in enumerate(zip(gx, rx)):
-        assert rel_err(a.grad, r.grad) < TOL, f"dgrad seg {i}"
+    # ---- HIP ("offset": a second run on inputs that are contiguous views at a one-float storage offset)
+    fwd_plans = []
+    for offset in ((False, True) if "offset" in name else (False,)):
+        gx = [(torch.empty(x.numel() + 1, device=DEV)[1:].view(x.shape).copy_(x) if offset else x.clone().to(DEV))
+              .requires_grad_(True) for x in xs]
+        gw, gb = wt.clone().to(DEV).requires_grad_(True), b.clone().to(DEV).requires_grad_(True)
+        L.PLAN_LOG = set()
+        try:
+            out = ConvFn.apply(gw, gb, (k, stride, pad, opad, transposed, act, alpha, beta, out_hw), *gx)
+        finally:
+            fwd_plans.append(sorted(r for r in L.PLAN_LOG if r[0] == "fwd"))
+            L.PLAN_LOG = None
+        assert out.shape == ref.shape
+        (out * gout.to(DEV)).sum().backward()
+        assert rel_err(out, ref) < TOL, ("forward", offset)
+        assert rel_err(gw.grad, rw.grad) < TOL, ("wgrad", offset)
+        assert rel_err(gb.grad, rb.grad) < TOL, ("bias grad", offset)
+        for i, (a, r) in enumerate(zip(gx, rx)):
+            assert rel_err(a.grad, r.grad) < TOL, (f"dgrad seg {i}", offset)
+    if "offset" in name:
+        aligned, unaligned = fwd_plans
+        assert [r[1] for r in aligned] == [1] and (aligned[0][12] >> 8) & 1, ("aligned: conv_pipe, 16-byte lanes", aligned)
+        assert unaligned and 1 not in [r[1] for r in unaligned], ("offset: unpacked kernels", unaligned)
 
 
 def test_conv_input_without_grad_skips_dgrad():
@@ -168,7 +184,8 @@ FUSE_CASES = [
 
 @pytest.mark.parametrize("case", FUSE_CASES, ids=[c[0] for c in FUSE_CASES])
 def test_fused_relu_backward(case):
-    """ReLU backward + bias gradient of a producing layer done by its consumers' dgrad kernels (dvf_conv2d_dgrad_masked):
+    """ReLU backward of a producing layer done by its consumers' dgrad kernels (dvf_conv2d_dgrad with mask_segs), its bias
+    gradient by its own weight-gradient kernel (dvf_conv2d_wgrad):
     y = relu(convA(x)) feeds a 3x3 conv, a stride-2 conv / transposed conv and a 1-channel head; every gradient is
     compared with torch CPU, and with the unfused path (FUSE_RELU_BWD = False) of this library."""
     from dvf import conv as C

@@ -21,8 +21,8 @@ for name, segs, cout, k, s, p, (n, h, w) in LAYERS:
     res = {}
     for mode in ("atomic", "det"):
         def call():
-            L.check(lib.dvf_conv2d_wgrad_det(ctypes.byref(d), L.ptr_array(xs), L.int_array(segs), len(segs), L.dev(dpre), L.dev(dw), 1, L.dev(db), 1,
-                                             L.dev(ws) if mode == "det" else None, wsf if mode == "det" else 0, L.stream()), "wgrad")
+            L.check(lib.dvf_conv2d_wgrad(ctypes.byref(d), L.ptr_array(xs), L.int_array(segs), len(segs), L.dev(dpre), L.dev(dw), 1, L.dev(db), 1,
+                                         L.dev(ws) if mode == "det" else None, wsf if mode == "det" else 0, L.stream()), "wgrad")
         for _ in range(3): call()
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
