@@ -1,5 +1,13 @@
-// Host side of the pipelined convolution (included by conv.hip inside its anonymous namespace): weight packing,
-// split-K reduction, planning and launch.
+// Host side of the pipelined convolution (conv.hip): weight packing, the finishing passes of a split launch, planning
+// and launch.
+#pragma once
+#include <string.h>
+#include "dvf_common.h"
+#include "conv_pipe.h"
+#include "conv_op.h"
+
+namespace {
+
 using dvfp::PClass;
 using dvfp::PipeArgs;
 using dvfp::PipeGeo;
@@ -157,6 +165,17 @@ __global__ __launch_bounds__(256) void conv_pack_batch_kernel(const PackArgs *jo
     pack_block(a, local % a.NCH, local / a.NCH, S);
 }
 
+// y = act(y + bias[c]) in place: finishes a split-K convolution.
+__global__ void bias_act_kernel(float *y, const float *bias, int C, int64_t HW, int64_t total, int act, float alpha,
+                                float beta) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)((i / HW) % C);
+        float v = y[i];
+        if (bias) v += bias[c];
+        y[i] = dvfp::apply_act(v, act, alpha, beta);
+    }
+}
+
 // out = act(sum_k ws[k] + bias): finishes a split-K convolution whose blocks stored plain partial tiles.
 __global__ void splitk_reduce_kernel(const float *ws, float *out, const float *bias, int KS, int64_t slice, int C, int64_t HW,
                                      int act, float alpha, float beta) {
@@ -222,10 +241,13 @@ int g_stamp_blocks = 0;
 #endif
 // ---------------------------------------------------------------------------------------- host planning
 struct PipePlan {
+    PipeArgs a;              // geometry and tiling; the operands are set at launch
     int MT, NT, WM, CKH, TBU, threads;
     size_t lds;
     dim3 grid;
-    int64_t packed_floats, ws_floats;
+    int64_t packed_floats;   // the op's share of the packed-weight buffer
+    int64_t ws_floats;       // split-K workspace the launch can use (0: none)
+    size_t pack_lds;         // LDS tile of the packing kernel
 };
 
 struct PipeOverride { int on, MT, NT, WM, CK, KS, BN, NST; };
@@ -264,18 +286,20 @@ inline PipeTiles pipe_tiles(int OHc, int OWc, int N, int ntile, int BNwant, int 
 }
 
 
-// Plan one op (all its classes share the launch).  Fills `a`'s tiling/packing fields; the same plan drives packing.
-int plan_pipe(PipeArgs &a, const ClassSpec *cls, int ncls, PipePlan &pl, bool head_fwd = false) {
-    if (ncls < 1 || ncls > 4) return DVF_ERR_INVALID_ARG;
+// Plan one op (all its classes share the launch): pure, geometry in, plan out.  The same plan drives packing and launch.
+// DVF_ERR_UNSUPPORTED: the op is outside the pipelined kernel's envelope (the unpacked kernels take it).
+int plan_pipe(const ConvOp &op, PipePlan &pl) {
+    if (op.ncls < 1) return DVF_ERR_UNSUPPORTED;
+    const ClassSpec *cls = op.cls;
+    const int ncls = op.ncls, Tmax = op.Tmax, TAmax = op.TAmax, TBmax = op.TBmax, OHc = op.OHc, OWc = op.OWc;
+    const bool head_fwd = op.head_fwd;
+    PipeArgs &a = pl.a;
+    a = PipeArgs{};
+    for (int s = 0; s < op.nseg; ++s) a.segC[s] = op.segC[s];
+    a.nseg = op.nseg; a.M = op.M;
+    a.N = op.N; a.IH = op.IH; a.IW = op.IW; a.OH = op.OH; a.OW = op.OW;
+    a.act = op.act; a.alpha = op.alpha; a.beta = op.beta;
     a.ncls = ncls; a.OS = cls[0].OS; a.IS = cls[0].IS;
-    int Tmax = 0, TAmax = 0, TBmax = 0, OHc = 0, OWc = 0;
-    for (int i = 0; i < ncls; ++i) {
-        const ClassSpec &c = cls[i];
-        const int T = c.TA * c.TB;
-        if (T < 1 || c.OHc <= 0 || c.OWc <= 0) return DVF_ERR_INVALID_ARG;
-        Tmax = T > Tmax ? T : Tmax; TAmax = c.TA > TAmax ? c.TA : TAmax; TBmax = c.TB > TBmax ? c.TB : TBmax;
-        OHc = c.OHc > OHc ? c.OHc : OHc; OWc = c.OWc > OWc ? c.OWc : OWc;
-    }
     const PipeOverride ov = pipe_override();
     // Layers with at most 16 output channels stay on the register-staged conv_gather_kernel (half of a 32-row MFMA tile would
     // be padding); 17..32 channels run here since round 3 (with the rewritten producers the pipelined kernel wins for the 3x3
@@ -299,7 +323,6 @@ int plan_pipe(PipeArgs &a, const ClassSpec *cls, int ncls, PipePlan &pl, bool he
     int TBU = TBmax;
     if (TBU == 6) TBU = 7;
     if (TBU > 7) return DVF_ERR_UNSUPPORTED;
-    (void)Tmax;
     // --- block shape: channels per block (32*MT*WM) and pixel tiles per block (WN*NT)
     int MT = a.M > 32 ? 2 : 1;
     int BN = 1;
@@ -336,7 +359,7 @@ int plan_pipe(PipeArgs &a, const ClassSpec *cls, int ncls, PipePlan &pl, bool he
     a.tilesX = cdiv(OWc, a.BW); a.tilesY = cdiv(OHc, a.BH); a.NG = cdiv(a.N, a.BN);
     const int SW = 1 << a.lsw, SH = 1 << a.lsh, MB = 32 * MT * WM;
     // patch DMA in 16-byte lanes (pipe_geo): image rows and tile origins must be 16-byte aligned (the tensor base pointers
-    // are checked at launch, pipe_run).  The wider rows cost LDS: where they would push the chunk depth below what 4-byte
+    // are checked at launch, run_pipe).  The wider rows cost LDS: where they would push the chunk depth below what 4-byte
     // lanes allow, the deeper chunks win (profiles/r03_pipe_stamps_after.txt: 3x3 128->128 @32x104, CK 16 vs 8).
     auto slab = [&](int CK, int TA) { return (TA * TBU * CK * MB + 255) & ~255; };
     static const int ks_thr = dvf_tune("DVF_PIPE_KSTHR") ? atoi(dvf_tune("DVF_PIPE_KSTHR")) : 160;       // tuning knobs
@@ -404,10 +427,12 @@ int plan_pipe(PipeArgs &a, const ClassSpec *cls, int ncls, PipePlan &pl, bool he
     if (KS < 1) KS = 1;
     if ((int64_t)a.NG * KS * ncls > 65535) return DVF_ERR_UNSUPPORTED;
     a.KS = KS;
-    pl.ws_floats = KS > 1 ? (int64_t)KS * a.N * a.M * a.OH * a.OW : 0;
+    pl.ws_floats = (op.covers && KS > 1) ? (int64_t)KS * a.N * a.M * a.OH * a.OW : 0;
     for (int s2 = 0; s2 < a.nseg; ++s2)
         if ((int64_t)a.N * a.segC[s2] * a.IH * a.IW * 4 >= ((int64_t)1 << 31) - 16) return DVF_ERR_UNSUPPORTED;
     pl.MT = MT; pl.NT = NT; pl.WM = WM; pl.CKH = CK / 2; pl.TBU = TBU; pl.lds = dd.lds;
+    pl.pack_lds = (size_t)32 * ((CK * op.KK) | 1) * sizeof(float);
+    if (pl.pack_lds > 64 * 1024) return DVF_ERR_UNSUPPORTED;
     pl.grid = dim3(a.tilesX * a.tilesY, mblocks, a.NG * KS * ncls);
     // Blocked accumulation (conv_pipe.h): the accumulators are banked every `blk` chunks.  Product policy = round 2/3's: every
     // chunk, in the deep layers only (64-channel waves, 8/16-channel chunks of 2-4-tap rows, a K range of >= 512 terms on a
@@ -454,31 +479,25 @@ int launch_pipe(const PipeArgs &a, const PipePlan &pl, hipStream_t st) {
     return launch_pipe_family<1, 1, 1>(a, pl.CKH, pl.TBU, pl.grid, pl.lds, st, pl.threads);
 }
 
-// One op instance = one (M range, reduction segments, classes) triple: Conv2d fwd, one segment of a dgrad, ...
-struct PipeOp {
-    PipeArgs a;
-    ClassSpec cls[4];
-    int ncls;
-    bool covers;
-    int w_mode, Mtot, Rtot, KK, m_base;
-    bool head_fwd;       // forward of a Conv2d (make_fwd_op): the 1-4 channel heads over >= 128 channels may run here
-};
-
-// ws: optional split-K workspace (ws_floats floats).  With it the K-splits store plain partial tiles and one pass
-// reduces them (+bias, activation); without it they accumulate with float atomics into a zeroed output.
-int pipe_run(PipeOp &op, const float *packed, float *ws, int64_t ws_floats, hipStream_t st) {
-    PipePlan pl;
-    int rc = plan_pipe(op.a, op.cls, op.ncls, pl, op.head_fwd);
-    if (rc) return rc;
-    PipeArgs &a = op.a;
-    a.wp = packed;
+// Launch a planned op.  ws: optional split-K workspace (ws_floats floats).  With it the K-splits store plain partial tiles
+// and one pass reduces them (+bias, activation); without it they accumulate with float atomics into a zeroed output.
+// DVF_ERR_UNSUPPORTED, before anything is noted or launched: an operand of a 16-byte-lane plan is not 16-byte aligned.
+int run_pipe(const ConvOp &op, const PipePlan &pl, const ConvIO &io, const float *packed, float *ws, int64_t ws_floats,
+             hipStream_t st) {
+    PipeArgs a = pl.a;
+    for (int s = 0; s < a.nseg; ++s) {
+        a.in[s] = io.in[s];
+        if (a.x4 && (reinterpret_cast<uintptr_t>(a.in[s]) & 15)) return DVF_ERR_UNSUPPORTED;    // (a view at an odd element offset)
+    }
+    a.wp = packed; a.bias = io.bias; a.mask = io.mask;
+    float *out = io.out;
     const int64_t HW = (int64_t)a.OH * a.OW, total = (int64_t)a.N * a.M * HW;
-    float *out = a.out;
     int mode = 0;
     if (!op.covers) mode = 1;
     else if (a.KS > 1) mode = (ws && ws_floats >= pl.ws_floats) ? 2 : 1;
     if (mode == 1 && hipMemsetAsync(out, 0, sizeof(float) * total, st) != hipSuccess) return DVF_ERR_LAUNCH;
     a.out_mode = mode;
+    a.out = out;
     if (mode == 2) { a.out = ws; a.ws_slice = total; }
     if (const char *e = dvf_tune("DVF_DBG")) a.dbg = atoi(e);
     a.stamps = nullptr;
@@ -493,15 +512,12 @@ int pipe_run(PipeOp &op, const float *packed, float *ws, int64_t ws_floats, hipS
         }
     }
 #endif
-    if (a.x4)
-        for (int s2 = 0; s2 < a.nseg; ++s2)
-            if (reinterpret_cast<uintptr_t>(a.in[s2]) & 15) return DVF_ERR_UNSUPPORTED;    // (a view at an odd element offset)
     dvf_plan_note(DVF_K_PIPE, pl.MT, pl.NT, pl.WM, 2 * pl.CKH, pl.TBU, a.KS, a.BN, a.NST, pl.threads, (int)pl.lds, mode | (a.ncls << 4) | (a.x4 << 8) | ((a.blk ? 1 : 0) << 9));
     if (dvf_tune("DVF_PIPE_DEBUG"))
         fprintf(stderr, "[pipe] M %d chunks %d N %d out %dx%d cls %d | MT %d NT %d WM %d CK %d TBU %d KS %d BN %d tile %dx%d "
                 "(sub %dx%d) grid %ux%ux%u lds %zu x%d mode %d\n", a.M, a.NCH, a.N, a.OH, a.OW, a.ncls, pl.MT, pl.NT, pl.WM,
                 2 * pl.CKH, pl.TBU, a.KS, a.BN, a.BH, a.BW, 1 << a.lsh, 1 << a.lsw, pl.grid.x, pl.grid.y, pl.grid.z, pl.lds, a.NST, mode);
-    rc = launch_pipe(a, pl, st);
+    int rc = launch_pipe(a, pl, st);
     if (rc) return rc;
     const int64_t nb = (total + 255) / 256;
     if (mode == 2 && a.KS >= 8 && HW < ((int64_t)1 << 30)) {
@@ -527,16 +543,10 @@ int pipe_run(PipeOp &op, const float *packed, float *ws, int64_t ws_floats, hipS
     return DVF_OK;
 }
 
-int pipe_pack(PipeOp &op, const float *w, float *packed, int64_t *nfloats, int64_t *wsfloats, hipStream_t st,
-              PackArgs *job_out = nullptr, int *job_blocks = nullptr) {
-    PipePlan pl;
-    int rc = plan_pipe(op.a, op.cls, op.ncls, pl, op.head_fwd);
-    if (rc) return rc;
-    if ((size_t)32 * ((2 * pl.CKH * op.KK) | 1) * sizeof(float) > 64 * 1024) return DVF_ERR_UNSUPPORTED;   // pack kernel's LDS tile
-    if (nfloats) *nfloats = pl.packed_floats;
-    if (wsfloats) *wsfloats = op.covers ? pl.ws_floats : 0;
-    if (!w || !packed) return DVF_OK;                       // size query only
-    const PipeArgs &a = op.a;
+// The packing job of a planned op: w (the layer's stored weights) -> packed (the op's share of the packed buffer).
+// *blocks: its grid, NCH chunks x 32-channel m-tiles; its LDS is pl.pack_lds.
+PackArgs pack_job(const ConvOp &op, const PipePlan &pl, const float *w, float *packed, int *blocks) {
+    const PipeArgs &a = pl.a;
     PackArgs p{};
     p.w = w; p.wp = packed; p.w_mode = op.w_mode; p.Mtot = op.Mtot; p.Rtot = op.Rtot; p.KK = op.KK;
     p.m_base = op.m_base; p.M = a.M; p.nseg = a.nseg;
@@ -550,15 +560,16 @@ int pipe_pack(PipeOp &op, const float *w, float *packed, int64_t *nfloats, int64
         p.wp_off[c] = a.cls[c].wp_off;
         for (int t = 0; t < op.cls[c].TA * op.cls[c].TB; ++t) p.tapmap[c][t] = (signed char)op.cls[c].tapmap[t];
     }
-    const size_t lds = (size_t)32 * ((p.CK * p.KK) | 1) * sizeof(float);
-    if (lds > 64 * 1024) return DVF_ERR_UNSUPPORTED;
-    const int mtiles = cdiv(a.M, p.MB) * (p.MB >> 5);
-    if (job_out) {                                          // export for dvf_conv2d_pack_batch instead of launching
-        *job_out = p;
-        *job_blocks = a.NCH * mtiles;
-        return DVF_OK;
-    }
-    conv_pack_kernel<<<dim3(a.NCH, mtiles), 256, lds, st>>>(p);
+    *blocks = a.NCH * cdiv(a.M, p.MB) * (p.MB >> 5);
+    return p;
+}
+
+int launch_pack(const ConvOp &op, const PipePlan &pl, const float *w, float *packed, hipStream_t st) {
+    int blocks;
+    const PackArgs p = pack_job(op, pl, w, packed, &blocks);
+    conv_pack_kernel<<<dim3(p.NCH, blocks / p.NCH), 256, pl.pack_lds, st>>>(p);
     DVF_LAUNCH_CHECK();
     return DVF_OK;
 }
+
+}  // namespace
