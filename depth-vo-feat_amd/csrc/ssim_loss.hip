@@ -1,0 +1,311 @@
+// Opt-in appearance term: alpha * DSSIM + (1 - alpha) * L1 between a target image x and an already warped reference y
+// (monodepth2 form; the reference has no SSIM -- SURVEY.md preamble #1 -- so there is no reference call site and parity is
+// UNPINNED; tests/ check this kernel pair against a torch restatement in fp64).  Definition, per image n and channel c, with
+// x = fl(in_scale * tgt), y = fl(in_scale * warped):
+//   3x3 window, uniform weights 1/9, REFLECTION border (index -1 -> 1, H -> H-2; same for W):
+//     mx, my = window means;  vx = mean((x - mx)^2), vy = mean((y - my)^2), cxy = mean((x - mx)(y - my))   (centred form)
+//   SSIM  = ((2 mx my + c1)(2 cxy + c2)) / ((mx^2 + my^2 + c1)(vx + vy + c2))
+//   dssim = clamp((1 - SSIM) / 2, 0, 1)                       (derivative 0 outside the clamp range)
+//   term  = alpha * dssim + (1 - alpha) * |x - y|
+//   valid = 1 - prod_c [y_c == 0] at the centre pixel (the reference's exact-zero mask; no gradient)
+//   loss  = sum(term * valid * m) / (B C H W)                 (m: optional explainability mask, receives a gradient)
+//
+// Forward: one block owns a 64x16 pixel tile of one image; per channel it stages x and y with halo 1 in LDS, each thread
+// evaluates 4 vertically adjacent windows, one partial per block, fixed-order reduce: the loss is bit-reproducible.
+// Backward: GATHER form, no atomics.  Within window q, d dssim_q / d y_j = Py_q + Q_q x_j + R_q y_j is affine in the tap's
+// own values (same for x with Px_q and x, y swapped), so per channel the block stages halo 2, computes the four
+// coefficients (times alpha * valid_q * m_q * gate_q * grad / N) of the halo-1 ring of windows once into LDS, and every pixel
+// sums the <= 9 windows that contain it -- a window that reaches the pixel through the reflected border counts twice per
+// axis -- plus its own L1 sign term.  Every output element is written exactly once.
+#include "dvf_common.h"
+
+namespace {
+
+constexpr int TW = 64, TH = 16, NT = 256;
+constexpr int SW = 72;                 // LDS row stride: tile column 0 sits at float 4 of a row, so 16-byte row pieces stay aligned
+constexpr int RW = TW + 2, RH = TH + 2;  // halo-1 ring of windows around the tile (backward)
+
+// reflect an index that is at most n-1 outside [0, n) (n >= 3); anything farther out is clamped (those values are never used)
+__device__ __forceinline__ int reflect_idx(int i, int n) {
+    i = i < 0 ? -i : i;
+    i = i >= n ? 2 * n - 2 - i : i;
+    return min(max(i, 0), n - 1);
+}
+
+// Stage rows y0-HALO .. y0+TH+HALO-1, columns x0-HALO .. x0+TW+HALO-1 of one plane (border reflected) times in_scale.
+template <int HALO>
+__device__ __forceinline__ void stage_plane(float *__restrict__ dst, const float *__restrict__ src, int H, int W, int y0, int x0,
+                                            float in_scale, int vec) {
+    constexpr int ROWS = TH + 2 * HALO;
+    for (int i = threadIdx.x; i < ROWS * (TW / 4); i += NT) {
+        const int r = i / (TW / 4), c4 = (i % (TW / 4)) * 4;
+        const float *row = src + (int64_t)reflect_idx(y0 - HALO + r, H) * W;
+        const int gx = x0 + c4;
+        float4 v;
+        if (vec && gx + 3 < W) {
+            v = *reinterpret_cast<const float4 *>(row + gx);
+        } else {
+            v.x = row[reflect_idx(gx, W)];
+            v.y = row[reflect_idx(gx + 1, W)];
+            v.z = row[reflect_idx(gx + 2, W)];
+            v.w = row[reflect_idx(gx + 3, W)];
+        }
+        v.x = __fmul_rn(in_scale, v.x);
+        v.y = __fmul_rn(in_scale, v.y);
+        v.z = __fmul_rn(in_scale, v.z);
+        v.w = __fmul_rn(in_scale, v.w);
+        *reinterpret_cast<float4 *>(dst + r * SW + 4 + c4) = v;
+    }
+    for (int i = threadIdx.x; i < ROWS * 2 * HALO; i += NT) {
+        const int r = i / (2 * HALO), k = i % (2 * HALO);
+        const int lc = k < HALO ? k - HALO : TW + k - HALO;      // tile-relative column
+        const float *row = src + (int64_t)reflect_idx(y0 - HALO + r, H) * W;
+        dst[r * SW + 4 + lc] = __fmul_rn(in_scale, row[reflect_idx(x0 + lc, W)]);
+    }
+}
+
+struct SsimWin { float mx, my, a1, a2, b1, b2, ssim, dssim, gate; };
+
+// Window whose top-left tap is at LDS offset o.
+__device__ __forceinline__ SsimWin ssim_window(const float *sx, const float *sy, int o, float c1, float c2) {
+    float x[9], y[9], sumx = 0.f, sumy = 0.f;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            x[3 * r + c] = sx[o + r * SW + c];
+            y[3 * r + c] = sy[o + r * SW + c];
+            sumx += x[3 * r + c];
+            sumy += y[3 * r + c];
+        }
+    constexpr float ninth = 1.f / 9.f;
+    SsimWin w;
+    w.mx = sumx * ninth;
+    w.my = sumy * ninth;
+    float vx = 0.f, vy = 0.f, cxy = 0.f;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const float dx = x[t] - w.mx, dy = y[t] - w.my;
+        vx += dx * dx;
+        vy += dy * dy;
+        cxy += dx * dy;
+    }
+    w.a1 = 2.f * w.mx * w.my + c1;
+    w.a2 = 2.f * (cxy * ninth) + c2;
+    w.b1 = w.mx * w.mx + w.my * w.my + c1;
+    w.b2 = (vx + vy) * ninth + c2;
+    w.ssim = (w.a1 * w.a2) / (w.b1 * w.b2);
+    const float d = 0.5f * (1.f - w.ssim);
+    w.gate = (d >= 0.f && d <= 1.f) ? 1.f : 0.f;
+    w.dssim = fminf(fmaxf(d, 0.f), 1.f);
+    return w;
+}
+
+__global__ __launch_bounds__(NT) void ssim_fwd_kernel(const float *tgt, const float *warped, const float *mask,
+                                                      int64_t mask_batch_stride, float *partials, int C, int H, int W,
+                                                      float in_scale, float alpha, float c1, float c2, int vec) {
+    __shared__ __attribute__((aligned(16))) float sx[(TH + 2) * SW];
+    __shared__ __attribute__((aligned(16))) float sy[(TH + 2) * SW];
+    __shared__ float red[NT / 64];
+    const int n = blockIdx.z, x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+    const int lx = threadIdx.x & 63, ly0 = (threadIdx.x >> 6) * 4, gx = x0 + lx;
+    const int64_t plane = (int64_t)H * W;
+    const float *X = tgt + (int64_t)n * C * plane, *Y = warped + (int64_t)n * C * plane;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    bool nonzero[4] = {false, false, false, false};
+    for (int c = 0; c < C; ++c) {
+        __syncthreads();
+        stage_plane<1>(sx, X + c * plane, H, W, y0, x0, in_scale, vec);
+        stage_plane<1>(sy, Y + c * plane, H, W, y0, x0, in_scale, vec);
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (gx >= W || y0 + ly0 + k >= H) continue;
+            const int o = (ly0 + k) * SW + lx + 3;
+            const SsimWin w = ssim_window(sx, sy, o, c1, c2);
+            const float xc = sx[o + SW + 1], yc = sy[o + SW + 1];
+            acc[k] += alpha * w.dssim + (1.f - alpha) * fabsf(xc - yc);
+            nonzero[k] |= (yc != 0.f);
+        }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int gy = y0 + ly0 + k;
+        if (gx < W && gy < H && nonzero[k])
+            s += mask ? acc[k] * mask[(int64_t)n * mask_batch_stride + (int64_t)gy * W + gx] : acc[k];
+    }
+    s = wave_sum(s);
+    if (lx == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int64_t blk = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        partials[blk] = (red[0] + red[1]) + (red[2] + red[3]);
+    }
+}
+
+__global__ __launch_bounds__(256) void ssim_reduce_kernel(const float *partials, int64_t nblk, float scale, float *loss_out,
+                                                          int accumulate) {
+    __shared__ float red[4];
+    float s = 0.f;
+    for (int64_t i = threadIdx.x; i < nblk; i += 256) s += partials[i];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float t = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
+        loss_out[0] = accumulate ? loss_out[0] + t : t;
+    }
+}
+
+// how often window q (0 <= q < n) reads pixel p = q + d, |d| <= 1, through its three taps along one axis
+__device__ __forceinline__ float tap_count(int p, int q, int n) {
+    if (q < 0 || q >= n) return 0.f;
+    return ((q == 0 && p == 1) || (q == n - 1 && p == n - 2)) ? 2.f : 1.f;
+}
+
+__global__ __launch_bounds__(NT) void ssim_bwd_kernel(const float *tgt, const float *warped, const float *mask,
+                                                      int64_t mask_batch_stride, const float *grad_loss, float *g_warped,
+                                                      float *g_tgt, float *g_mask, int C, int H, int W, float in_scale, float alpha,
+                                                      float c1, float c2, float inv_n, int vec) {
+    __shared__ __attribute__((aligned(16))) float sx[(TH + 4) * SW];
+    __shared__ __attribute__((aligned(16))) float sy[(TH + 4) * SW];
+    __shared__ __attribute__((aligned(16))) float4 coef[RH * RW];   // (Px, Py, Q, R) of each ring window, weighted
+    __shared__ float sd[RH * RW];                                   // alpha * dssim of each ring window
+    __shared__ float swt[RH * RW];                                  // valid * m * grad_loss / N of each ring pixel (0 outside the image)
+    const int n = blockIdx.z, x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+    const int lx = threadIdx.x & 63, ly0 = (threadIdx.x >> 6) * 4, gx = x0 + lx;
+    const int64_t plane = (int64_t)H * W;
+    const float *X = tgt + (int64_t)n * C * plane, *Y = warped + (int64_t)n * C * plane;
+    const float gl = grad_loss[0] * inv_n;
+
+    for (int i = threadIdx.x; i < RH * RW; i += NT) {
+        const int qy = y0 - 1 + i / RW, qx = x0 - 1 + i % RW;
+        float wt = 0.f;
+        if (qy >= 0 && qy < H && qx >= 0 && qx < W) {
+            const int64_t p = (int64_t)qy * W + qx;
+            bool nz = false;
+            for (int c = 0; c < C; ++c) nz |= (__fmul_rn(in_scale, Y[c * plane + p]) != 0.f);
+            if (nz) wt = mask ? gl * mask[(int64_t)n * mask_batch_stride + p] : gl;
+        }
+        swt[i] = wt;
+    }
+    float gm[4] = {0.f, 0.f, 0.f, 0.f};
+    bool nonzero[4] = {false, false, false, false};
+    for (int c = 0; c < C; ++c) {
+        __syncthreads();
+        stage_plane<2>(sx, X + c * plane, H, W, y0, x0, in_scale, vec);
+        stage_plane<2>(sy, Y + c * plane, H, W, y0, x0, in_scale, vec);
+        __syncthreads();
+        for (int i = threadIdx.x; i < RH * RW; i += NT) {
+            const int ry = i / RW, rx = i % RW;
+            const float wt = swt[i];
+            float4 k = make_float4(0.f, 0.f, 0.f, 0.f);
+            float d = 0.f;
+            if (y0 - 1 + ry >= 0 && y0 - 1 + ry < H && x0 - 1 + rx >= 0 && x0 - 1 + rx < W) {
+                const SsimWin w = ssim_window(sx, sy, ry * SW + rx + 2, c1, c2);
+                constexpr float ninth = 1.f / 9.f;
+                const float ib = 1.f / (w.b1 * w.b2);
+                const float Q = 2.f * ninth * w.a1 * ib;                        // d SSIM / d cxy * (1/9) ... per tap
+                const float R = -2.f * ninth * w.ssim / w.b2;
+                const float Px = ninth * (2.f * w.my * w.a2 * ib - 2.f * w.mx * w.ssim / w.b1) - Q * w.my - R * w.mx;
+                const float Py = ninth * (2.f * w.mx * w.a2 * ib - 2.f * w.my * w.ssim / w.b1) - Q * w.mx - R * w.my;
+                const float f = -0.5f * alpha * w.gate * wt;                    // dssim = (1 - SSIM) / 2
+                k = make_float4(f * Px, f * Py, f * Q, f * R);
+                d = alpha * w.dssim;
+            }
+            coef[i] = k;
+            sd[i] = d;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ly = ly0 + r, gy = y0 + ly;
+            if (gx >= W || gy >= H) continue;
+            float ax = 0.f, ay = 0.f, q = 0.f, rr = 0.f;
+#pragma unroll
+            for (int dy = -1; dy <= 1; ++dy) {
+                const float wy = tap_count(gy, gy + dy, H);
+#pragma unroll
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const float wgt = wy * tap_count(gx, gx + dx, W);
+                    const float4 k = coef[(ly + 1 + dy) * RW + lx + 1 + dx];
+                    ax += wgt * k.x;
+                    ay += wgt * k.y;
+                    q += wgt * k.z;
+                    rr += wgt * k.w;
+                }
+            }
+            const float xc = sx[(ly + 2) * SW + lx + 4], yc = sy[(ly + 2) * SW + lx + 4];
+            const float diff = yc - xc;
+            const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
+            const float l1 = (1.f - alpha) * swt[(ly + 1) * RW + lx + 1] * sgn;
+            const int64_t o = ((int64_t)n * C + c) * plane + (int64_t)gy * W + gx;
+            if (g_warped) g_warped[o] = in_scale * (ay + q * xc + rr * yc + l1);
+            if (g_tgt) g_tgt[o] = in_scale * (ax + q * yc + rr * xc - l1);
+            gm[r] += sd[(ly + 1) * RW + lx + 1] + (1.f - alpha) * fabsf(diff);
+            nonzero[r] |= (yc != 0.f);
+        }
+    }
+    if (g_mask) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ly = ly0 + r, gy = y0 + ly;
+            if (gx >= W || gy >= H) continue;
+            g_mask[(int64_t)n * mask_batch_stride + (int64_t)gy * W + gx] = nonzero[r] ? gl * gm[r] : 0.f;
+        }
+    }
+}
+
+inline dim3 ssim_grid(int B, int H, int W) { return dim3((W + TW - 1) / TW, (H + TH - 1) / TH, B); }
+
+inline bool ssim_shape_ok(int B, int C, int H, int W) {
+    return B > 0 && C > 0 && H >= 3 && W >= 3 && B <= 65535 && (int64_t)C * H * W < ((int64_t)1 << 31);
+}
+
+inline int ssim_vec(const float *a, const float *b, int W) {
+    return (W % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0) ? 1 : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t dvf_ssim_partials_floats(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    const dim3 g = ssim_grid(B, H, W);
+    return (int64_t)g.x * g.y * g.z;
+}
+
+int dvf_ssim_loss_fwd(const float *tgt, const float *warped, const float *mask, int64_t mask_batch_stride, float *loss_out,
+                      float *partials, int B, int C, int H, int W, float in_scale, float alpha, float c1, float c2, int accumulate,
+                      void *stream) {
+    if (!tgt || !warped || !loss_out || !partials || !ssim_shape_ok(B, C, H, W) || (mask && mask_batch_stride < (int64_t)H * W))
+        return DVF_ERR_INVALID_ARG;
+    hipStream_t st = dvf_stream(stream);
+    const dim3 grid = ssim_grid(B, H, W);
+    ssim_fwd_kernel<<<grid, NT, 0, st>>>(tgt, warped, mask, mask_batch_stride, partials, C, H, W, in_scale, alpha, c1, c2,
+                                         ssim_vec(tgt, warped, W));
+    DVF_LAUNCH_CHECK();
+    const float scale = (float)(1.0 / ((double)B * C * H * W));
+    ssim_reduce_kernel<<<1, 256, 0, st>>>(partials, (int64_t)grid.x * grid.y * grid.z, scale, loss_out, accumulate);
+    DVF_LAUNCH_CHECK();
+    return DVF_OK;
+}
+
+int dvf_ssim_loss_bwd(const float *tgt, const float *warped, const float *mask, int64_t mask_batch_stride, const float *grad_loss,
+                      float *g_warped, float *g_tgt, float *g_mask, int B, int C, int H, int W, float in_scale, float alpha,
+                      float c1, float c2, void *stream) {
+    if (!tgt || !warped || !grad_loss || !ssim_shape_ok(B, C, H, W) ||
+        ((mask || g_mask) && mask_batch_stride < (int64_t)H * W))
+        return DVF_ERR_INVALID_ARG;
+    if (!g_warped && !g_tgt && !g_mask) return DVF_OK;
+    const float inv_n = (float)(1.0 / ((double)B * C * H * W));
+    ssim_bwd_kernel<<<ssim_grid(B, H, W), NT, 0, dvf_stream(stream)>>>(tgt, warped, mask, mask_batch_stride, grad_loss, g_warped,
+                                                                       g_tgt, g_mask, C, H, W, in_scale, alpha, c1, c2, inv_n,
+                                                                       ssim_vec(tgt, warped, W));
+    DVF_LAUNCH_CHECK();
+    return DVF_OK;
+}
+
+}  // extern "C"

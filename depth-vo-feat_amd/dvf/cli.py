@@ -30,10 +30,21 @@ def add_common_flags(parser):
                         "parameters when the feature term is on (the photometric backward scatters the source-feature "
                         "gradients, and the depthwise up-convolutions sum their weight gradients, with float atomics); "
                         "costs ~5 %% of a step")
+    g.add_argument("--ssim-weight", type=float, default=0.0, metavar="A",
+                   help="A > 0: the image photometric term becomes A * DSSIM + (1 - A) * L1 (monodepth2 form, 3x3 reflected "
+                        "windows; 0.85 is the usual choice); 0 = the reference's L1.  The reference has no SSIM: parity unpinned")
+    g.add_argument("--ssim-c1", type=float, default=1e-4, metavar="C1",
+                   help="SSIM luminance constant, 0.01^2 for a unit value range (train.py feeds [-1, 1], unsupervise.py 0.004 * img)")
+    g.add_argument("--ssim-c2", type=float, default=9e-4, metavar="C2", help="SSIM contrast constant, 0.03^2 for a unit value range")
     g.add_argument("--reference-stereo-pose", action="store_true",
                    help="feed the dataset's T_R2L file vector (0,0,0,Tx,0,0) unchanged into pose_vec2mat / the stereo-pose "
                         "MSE target, exactly as the reference does (unsupervise.py:101, train.py:201); default: convert it "
                         "to the (t, r-euler) order those functions read (un_dataset.to_batch)")
+
+
+def ssim_kwargs(args):
+    """The --ssim-* flags as keywords of the step bodies (dvf/steps.py)."""
+    return {"ssim_weight": args.ssim_weight, "ssim_c1": args.ssim_c1, "ssim_c2": args.ssim_c2}
 
 
 def init_distributed():

@@ -112,6 +112,66 @@ class PhotoLossFn(torch.autograd.Function):
         return (g_tgt, g_depth, g_pose, None, None, g_mask, None, *g_srcs)
 
 
+class SsimL1LossFn(torch.autograd.Function):
+    """alpha * DSSIM + (1 - alpha) * L1 between a target and an already warped reference, exact-zero and explainability
+    masked, mean over B*C*H*W (csrc/ssim_loss.hip; build-side extension, the reference has no SSIM).
+
+    Inputs: tgt, warped [B,C,H,W]; mask None, [B,H,W] / [B,1,H,W], or [B,V,H,W] with a view index;
+    cfg = (in_scale, alpha, c1, c2, view_index or None).  Output: 0-dim loss."""
+
+    @staticmethod
+    def forward(ctx, tgt, warped, mask, cfg):
+        in_scale, alpha, c1, c2, view = cfg
+        tgt, warped = _f32c(tgt), _f32c(warped)
+        mask = _f32c(mask) if mask is not None else None
+        B, C, H, W = tgt.shape
+        if warped.shape != tgt.shape:
+            raise ValueError(f"warped {tuple(warped.shape)} does not match target {tuple(tgt.shape)}")
+        m_off, m_stride = 0, 0
+        ctx.mask_shape = mask.shape if mask is not None else None
+        if mask is not None:
+            if mask.dim() == 3:
+                mask = mask.unsqueeze(1)
+            V = mask.shape[1]
+            if tuple(mask.shape) != (B, V, H, W) or not 0 <= (view or 0) < V or (view is None and V != 1):
+                raise ValueError(f"mask {tuple(mask.shape)} / view {view} does not match target {tuple(tgt.shape)}")
+            m_off, m_stride = (view or 0) * H * W, V * H * W
+        lib = L.lib()
+        out = torch.empty(1, device=tgt.device)
+        partials = torch.empty(int(lib.dvf_ssim_partials_floats(B, H, W)), device=tgt.device)
+        fwd_bytes = float(B * H * W) * (8 * C + (4 if mask is not None else 0))
+        m_ptr = L.dev(mask, "mask")
+        with L.timed("ssim_fwd", 0.0, fwd_bytes):
+            L.check(lib.dvf_ssim_loss_fwd(L.dev(tgt, "tgt"), L.dev(warped, "warped"), m_ptr + 4 * m_off if mask is not None else None,
+                                          m_stride, L.dev(out), L.dev(partials), B, C, H, W, in_scale, alpha, c1, c2, 0,
+                                          L.stream()), "dvf_ssim_loss_fwd")
+        ctx.save_for_backward(tgt, warped, mask)
+        ctx.cfg, ctx.m_off, ctx.m_stride, ctx.fwd_bytes = (in_scale, alpha, c1, c2), m_off, m_stride, fwd_bytes
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gloss):
+        tgt, warped, mask = ctx.saved_tensors
+        B, C, H, W = tgt.shape
+        need = ctx.needs_input_grad
+        g_tgt = torch.empty_like(tgt) if need[0] else None
+        g_warped = torch.empty_like(warped) if need[1] else None
+        g_mask = None
+        if mask is not None and need[2]:
+            # the kernel writes the view it was given; the other views of a [B,V,H,W] mask get no gradient from this term
+            g_mask = torch.empty_like(mask) if mask.shape[1] == 1 else torch.zeros_like(mask)
+        in_scale, alpha, c1, c2 = ctx.cfg
+        off = 4 * ctx.m_off
+        bwd_bytes = ctx.fwd_bytes + float(B * H * W) * (4 * C * ((g_tgt is not None) + (g_warped is not None)) +
+                                                        (4 if g_mask is not None else 0))
+        with L.timed("ssim_bwd", 0.0, bwd_bytes):
+            L.check(L.lib().dvf_ssim_loss_bwd(L.dev(tgt), L.dev(warped), L.dev(mask) + off if mask is not None else None,
+                                              ctx.m_stride, L.dev(_f32c(gloss).reshape(1), "grad_loss"), L.dev(g_warped),
+                                              L.dev(g_tgt), L.dev(g_mask) + off if g_mask is not None else None,
+                                              B, C, H, W, in_scale, alpha, c1, c2, L.stream()), "dvf_ssim_loss_bwd")
+        return g_tgt, g_warped, g_mask.reshape(ctx.mask_shape) if g_mask is not None else None, None
+
+
 class SmoothLossFn(torch.autograd.Function):
     """smooth_loss over a list of maps (reference loss_functions.py:23-41, loss_functions_sfm.py:59-77):
     sum_s w_s * (mean|dx2| + mean|dxdy| + mean|dydx| + mean|dy2|), w_{s+1} = w_s / scale_factor."""

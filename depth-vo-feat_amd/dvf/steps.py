@@ -50,14 +50,17 @@ def _side_by_side(aux_fn, main_fn):
 
 
 def unsupervise_losses(depth_net, pose_net, batch, feat_extractor=None, img_scale=0.004, smooth_weight=10.0,
-                       feat_weight=0.1, depth_eps=1e-4):
+                       feat_weight=0.1, depth_eps=1e-4, ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4):
+    """unsupervise.py:83-111.  ssim_weight > 0 (extension): the image term becomes a * DSSIM + (1 - a) * L1; the feature
+    term stays L1."""
     R2, R1, L2 = batch["img_R2"], batch["img_R1"], batch["img_L2"]
     # unsupervise.py:92,95 (cat(R2, R1) done virtually) and :94 (intended: finest disparity)
     (_, T_2to1), disps = _side_by_side(lambda: pose_net((R2, R1)), lambda: depth_net(R2))
     inv_depth = disps[0]
     depth = reciprocal(inv_depth, depth_eps).squeeze(1)            # :99
     img_loss = LF.photometric_reconstruction_loss(R2, R1, L2, depth, T_2to1, batch["T_R2L"], batch["K"], batch["Kinv"],
-                                                  img_scale=img_scale)   # :101 (0.004 * img applied inside the kernel)
+                                                  img_scale=img_scale,   # :101 (0.004 * img applied inside the kernel)
+                                                  ssim_weight=ssim_weight, ssim_c1=ssim_c1, ssim_c2=ssim_c2)
     smooth = LF.smooth_loss(depth.unsqueeze(1))                    # :102
     terms = {"img": img_loss.detach(), "smooth": smooth.detach()}
     loss = img_loss + smooth_weight * smooth
@@ -87,15 +90,17 @@ def depth_only_losses(depth_net, batch, img_scale=0.004, smooth_weight=10.0, dep
 
 
 def train_sfm_losses(disp_net, pose_exp_net, batch, w1=1.0, w2=0.0, w3=0.1, smooth_factor=2.0,
-                     rotation_mode="euler", padding_mode="zeros", feat_extractor=None, feat_weight=0.1):
-    """train.py:179-203.  feat_extractor: BASELINE.json configs[3] (cfg 4) adds the feature-reconstruction term of
+                     rotation_mode="euler", padding_mode="zeros", feat_extractor=None, feat_weight=0.1,
+                     ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4):
+    """train.py:179-203.  ssim_weight > 0 (extension): the 4-scale photometric term becomes a * DSSIM + (1 - a) * L1.  feat_extractor: BASELINE.json configs[3] (cfg 4) adds the feature-reconstruction term of
     unsupervise.py:104-111 (single scale, finest depth, the network's two poses) to the 4-scale body."""
     tgt = batch["img_R2"]
     refs = [batch["img_R1"], batch["img_L2"]] + list(batch.get("extra_refs", []))[: pose_exp_net.nb_ref_imgs - 2]
     (masks, pose), disparities = _side_by_side(lambda: pose_exp_net(tgt, refs), lambda: disp_net(tgt))   # train.py:187,189
     depth = [reciprocal(d, 0.0) for d in disparities]              # :188
     l1 = LS.photometric_reconstruction_loss(tgt, refs, batch["K"], batch["Kinv"], depth, masks, pose,
-                                            rotation_mode, padding_mode)                           # :191
+                                            rotation_mode, padding_mode, ssim_weight=ssim_weight, ssim_c1=ssim_c1,
+                                            ssim_c2=ssim_c2)                                       # :191
     l3 = LS.smooth_loss(depth, smooth_factor)                      # :200
     l4 = torch.nn.functional.mse_loss(pose[:, 1], batch["T_R2L"])  # :201  (24 floats: left to torch)
     loss = w1 * l1 + w3 * l3 + l4

@@ -8,11 +8,15 @@ from dvf.ops import ExplainabilityLossFn, PhotoLossFn, SmoothLossFn
 
 def photometric_reconstruction_loss(tgt_img, ref_imgs, intrinsics, intrinsics_inv, depth, explainability_mask, pose,
                                     rotation_mode='euler', padding_mode='zeros', align_corners=False,
-                                    check_nan=False):
+                                    check_nan=False, ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4):
     """Sum over scales and reference views of the masked, explainability-weighted L1 between the target and
     the inverse-warped references (reference loss_functions_sfm.py:9-46).  One fused kernel per scale handles
     all views.  The reference's per-view NaN assert (:34) forces a device sync per view per scale; here it is
-    opt-in (``check_nan=True``) and done once on the summed loss."""
+    opt-in (``check_nan=True``) and done once on the summed loss.
+    ``ssim_weight`` (extension, default 0 = the reference's L1): a value a > 0 replaces |diff| by
+    a * DSSIM + (1 - a) * |diff| (monodepth2 form: 3x3 reflected windows, ``ssim_c1`` / ``ssim_c2`` for images in [-1, 1]).
+    The reference has no SSIM, so parity of this term is unpinned.  It is a composition, not the fused kernel: per scale and
+    view one inverse warp materialises the warped image, then dvf.ops.SsimL1LossFn."""
     if type(explainability_mask) not in [tuple, list]:
         explainability_mask = [explainability_mask]
     if type(depth) not in [list, tuple]:
@@ -29,6 +33,13 @@ def photometric_reconstruction_loss(tgt_img, ref_imgs, intrinsics, intrinsics_in
         refs_s = [area_downsample(r, (h, w)) for r in ref_imgs]          # :19
         k_s = torch.cat((intrinsics[:, 0:2] / downscale, intrinsics[:, 2:]), dim=1)               # :20
         kinv_s = torch.cat((intrinsics_inv[:, :, 0:2] * downscale, intrinsics_inv[:, :, 2:]), dim=2)   # :21
+        if ssim_weight > 0:
+            from dvf.ops import InverseWarpFn, SsimL1LossFn
+            for v, ref_s in enumerate(refs_s):
+                warped = InverseWarpFn.apply(ref_s, d[:, 0], pose[:, v], k_s, kinv_s, flags)
+                loss = loss + SsimL1LossFn.apply(tgt_s, warped, mask, (1.0, float(ssim_weight), float(ssim_c1), float(ssim_c2),
+                                                                        v if mask is not None else None))
+            continue
         loss = loss + PhotoLossFn.apply(tgt_s, d[:, 0], pose_vb6, k_s, kinv_s, mask, flags, *refs_s)
     if check_nan:
         assert((loss == loss).item() == 1)

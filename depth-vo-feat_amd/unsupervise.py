@@ -66,7 +66,7 @@ def main():
         n.to(args._device).train()
 
     def loss_fn(batch):
-        return unsupervise_losses(depth_net, odometry_net, batch, feat_extractor=feat)
+        return unsupervise_losses(depth_net, odometry_net, batch, feat_extractor=feat, **cli.ssim_kwargs(args))
 
     terms = ["total", "img", "smooth"] + (["feat"] if feat is not None else [])
     cli.run_training(args, nets, loss_fn, args.lr, (0.9, 0.999), args.weight_decay, terms, ckpts)

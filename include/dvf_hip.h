@@ -153,6 +153,32 @@ int64_t dvf_edge_smooth_partials_floats(int B, int H, int W);
 int dvf_edge_smooth_bwd(const float *inv_depth, const float *img, const float *grad_loss, float *g_inv_depth, int B, int C, int H,
                         int W, float in_scale, float edge_k, float weight, void *stream);
 
+/* ---------------------------------------------------------------- SSIM + L1 appearance term (build-side extension, opt-in)
+ * The reference has no SSIM (SURVEY.md preamble #1): there is NO reference call site.  The term plugs in where
+ * pytorch_version/loss_functions_sfm.py:23-35 / loss_functions.py:12-19 form `diff`, on an already warped reference
+ * (dvf_inverse_warp_fwd).  Definition (monodepth2 form), x = fl(in_scale * tgt), y = fl(in_scale * warped), both [B,C,H,W]:
+ *   per pixel and channel a 3x3 window, uniform weights 1/9, REFLECTION border (index -1 -> 1, H -> H-2, same for W):
+ *     mx, my, vx = mean((x - mx)^2), vy = mean((y - my)^2), cxy = mean((x - mx)(y - my))         (centred form)
+ *   SSIM  = ((2 mx my + c1)(2 cxy + c2)) / ((mx^2 + my^2 + c1)(vx + vy + c2))
+ *   dssim = clamp((1 - SSIM) / 2, 0, 1), derivative 0 outside the clamp range
+ *   term  = alpha * dssim + (1 - alpha) * |x - y|
+ *   valid = 1 - prod_c [y_c == 0] at the centre pixel (the reference's exact-zero mask), no gradient
+ *   loss_out[0] (+)= sum(term * valid * m) / (B C H W)   (masked pixels stay in the denominator; accumulate != 0 adds)
+ * mask: NULL or the explainability mask of this view, element (b, y, x) at mask[b * mask_batch_stride + y * W + x]
+ *   (view v of a [B,V,H,W] tensor: pointer + v*H*W, stride V*H*W -- no copy); it receives a gradient.
+ * partials: workspace >= dvf_ssim_partials_floats(B,H,W) floats; the loss is summed in a fixed order (bit-reproducible).
+ * Backward (gather form, no atomics): grad_loss is a DEVICE scalar; g_warped / g_tgt [B,C,H,W] and g_mask (addressed like
+ *   mask, same batch stride; = sum_c term * valid * grad_loss / (B C H W)) may each be NULL; every element of a given
+ *   output is written exactly once, nothing needs zeroing.
+ * DVF_ERR_INVALID_ARG for H or W < 3, C*H*W >= 2^31, B > 65535.  Parity unpinned (nothing in the reference to compare with). */
+int64_t dvf_ssim_partials_floats(int B, int H, int W);
+int dvf_ssim_loss_fwd(const float *tgt, const float *warped, const float *mask, int64_t mask_batch_stride, float *loss_out,
+                      float *partials, int B, int C, int H, int W, float in_scale, float alpha, float c1, float c2, int accumulate,
+                      void *stream);
+int dvf_ssim_loss_bwd(const float *tgt, const float *warped, const float *mask, int64_t mask_batch_stride, const float *grad_loss,
+                      float *g_warped, float *g_tgt, float *g_mask, int B, int C, int H, int W, float in_scale, float alpha,
+                      float c1, float c2, void *stream);
+
 /* ---------------------------------------------------------------- smoothness loss
  * Replaces one map of smooth_loss (loss_functions.py:23-41 ; loss_functions_sfm.py:59-77):
  * weight * (mean|dx2| + mean|dxdy| + mean|dydx| + mean|dy2|) of a [N,H,W] stack of planes (N = B*C).
