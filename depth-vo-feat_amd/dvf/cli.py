@@ -36,6 +36,13 @@ def add_common_flags(parser):
     g.add_argument("--ssim-c1", type=float, default=1e-4, metavar="C1",
                    help="SSIM luminance constant, 0.01^2 for a unit value range (train.py feeds [-1, 1], unsupervise.py 0.004 * img)")
     g.add_argument("--ssim-c2", type=float, default=9e-4, metavar="C2", help="SSIM contrast constant, 0.03^2 for a unit value range")
+    g.add_argument("--min-reprojection", action="store_true",
+                   help="the image appearance term (A * DSSIM + (1 - A) * L1, A = --ssim-weight, 0 allowed) takes the per-pixel "
+                        "minimum over the reference views instead of their sum (monodepth2 form); the explainability mask is "
+                        "not used in this mode (train.py: needs -m 0).  Not in the reference: parity unpinned")
+    g.add_argument("--auto-mask", action="store_true",
+                   help="with --min-reprojection: the unwarped reference views compete in the minimum, so pixels that do not "
+                        "move between frames are won by an identity candidate; the logged 'automask' is their share")
     g.add_argument("--reference-stereo-pose", action="store_true",
                    help="feed the dataset's T_R2L file vector (0,0,0,Tx,0,0) unchanged into pose_vec2mat / the stereo-pose "
                         "MSE target, exactly as the reference does (unsupervise.py:101, train.py:201); default: convert it "
@@ -45,6 +52,11 @@ def add_common_flags(parser):
 def ssim_kwargs(args):
     """The --ssim-* flags as keywords of the step bodies (dvf/steps.py)."""
     return {"ssim_weight": args.ssim_weight, "ssim_c1": args.ssim_c1, "ssim_c2": args.ssim_c2}
+
+
+def minreproj_kwargs(args):
+    """The --min-reprojection / --auto-mask flags as keywords of the step bodies (dvf/steps.py)."""
+    return {"min_reprojection": args.min_reprojection, "auto_mask": args.auto_mask}
 
 
 def init_distributed():

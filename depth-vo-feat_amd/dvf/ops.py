@@ -172,6 +172,66 @@ class SsimL1LossFn(torch.autograd.Function):
         return g_tgt, g_warped, g_mask.reshape(ctx.mask_shape) if g_mask is not None else None, None
 
 
+class MinReprojLossFn(torch.autograd.Function):
+    """Per-pixel minimum over the reference views of alpha * DSSIM + (1 - alpha) * L1, with an optional identity-reprojection
+    auto-mask (csrc/minreproj_loss.hip; build-side extension, monodepth2 form, nothing in the reference).
+
+    ``apply(tgt, cfg, n_views, *cands)``: tgt [B,C,H,W]; cfg = (in_scale, alpha, c1, c2, auto_mask); cands = the n_views warped
+    references (outputs of InverseWarpFn) and, with auto_mask, the n_views unwarped references in the same order.
+    Returns (loss 0-dim, select uint8 [B,H,W] with 255 = no usable candidate, counts int32 [K+1], the last one "none");
+    select and counts are not differentiable.  Gradients go to tgt and the warped candidates; an identity source must not
+    require one."""
+
+    @staticmethod
+    def forward(ctx, tgt, cfg, n_views, *cands):
+        in_scale, alpha, c1, c2, auto_mask = cfg
+        V, K = int(n_views), len(cands)
+        if not 1 <= V <= L.MAX_VIEWS:
+            raise ValueError(f"n_views must be 1..{L.MAX_VIEWS}, got {V}")
+        if K != (2 * V if auto_mask else V):
+            raise ValueError(f"expected {2 * V if auto_mask else V} candidates for {V} views (auto_mask={bool(auto_mask)}), got {K}")
+        for k, y in enumerate(cands):
+            if y.shape != tgt.shape:
+                raise ValueError(f"candidate {k} {tuple(y.shape)} does not match target {tuple(tgt.shape)}")
+            if k >= V and ctx.needs_input_grad[3 + k]:
+                raise ValueError(f"identity candidate {k} requires a gradient: the auto-mask sources are constants")
+        tgt = _f32c(tgt)
+        cands = [_f32c(y) for y in cands]
+        B, C, H, W = tgt.shape
+        lib = L.lib()
+        dev = tgt.device
+        out = torch.empty(1, device=dev)
+        select = torch.empty((B, H, W), device=dev, dtype=torch.uint8)
+        counts = torch.empty(K + 1, device=dev, dtype=torch.int32)
+        partials = torch.empty(int(lib.dvf_minreproj_partials_floats(B, H, W, K)), device=dev)
+        fwd_bytes = float(B * H * W) * (4 * C * (1 + K) + 1)         # target + K candidates read, selection written
+        with L.timed("minreproj_fwd", 0.0, fwd_bytes):
+            L.check(lib.dvf_minreproj_fwd(L.dev(tgt, "tgt"), L.ptr_array(cands, "cands"), V, int(bool(auto_mask)), L.dev(out),
+                                          select.data_ptr(), counts.data_ptr(), L.dev(partials), B, C, H, W, in_scale, alpha,
+                                          c1, c2, 0, L.stream()), "dvf_minreproj_fwd")
+        ctx.save_for_backward(tgt, select, *cands)
+        ctx.cfg, ctx.V, ctx.fwd_bytes = (in_scale, alpha, c1, c2, int(bool(auto_mask))), V, fwd_bytes
+        ctx.mark_non_differentiable(select, counts)
+        return out[0], select, counts
+
+    @staticmethod
+    def backward(ctx, gloss, _gselect, _gcounts):
+        tgt, select, *cands = ctx.saved_tensors
+        B, C, H, W = tgt.shape
+        V = ctx.V
+        need = ctx.needs_input_grad
+        g_tgt = torch.empty_like(tgt) if need[0] else None
+        g_warped = [torch.empty_like(cands[k]) if need[3 + k] else None for k in range(V)]
+        in_scale, alpha, c1, c2, auto_mask = ctx.cfg
+        n_grads = (g_tgt is not None) + sum(g is not None for g in g_warped)
+        bwd_bytes = ctx.fwd_bytes + float(B * H * W) * 4 * C * n_grads
+        with L.timed("minreproj_bwd", 0.0, bwd_bytes):
+            L.check(L.lib().dvf_minreproj_bwd(L.dev(tgt), L.ptr_array(cands), V, auto_mask, select.data_ptr(),
+                                              L.dev(_f32c(gloss).reshape(1), "grad_loss"), L.dev(g_tgt), L.ptr_array(g_warped),
+                                              B, C, H, W, in_scale, alpha, c1, c2, L.stream()), "dvf_minreproj_bwd")
+        return (g_tgt, None, None, *g_warped, *([None] * (len(cands) - V)))
+
+
 class SmoothLossFn(torch.autograd.Function):
     """smooth_loss over a list of maps (reference loss_functions.py:23-41, loss_functions_sfm.py:59-77):
     sum_s w_s * (mean|dx2| + mean|dxdy| + mean|dydx| + mean|dy2|), w_{s+1} = w_s / scale_factor."""

@@ -49,10 +49,20 @@ def _side_by_side(aux_fn, main_fn):
     return a_out, m_out
 
 
+def _identity_share(counts, n_views):
+    """Share of the pixels won by an identity candidate, from the selection counts of MinReprojLossFn (a handful of
+    integers: no image-sized kernel)."""
+    return counts[n_views:2 * n_views].sum() / counts.sum()
+
+
 def unsupervise_losses(depth_net, pose_net, batch, feat_extractor=None, img_scale=0.004, smooth_weight=10.0,
-                       feat_weight=0.1, depth_eps=1e-4, ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4):
+                       feat_weight=0.1, depth_eps=1e-4, ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4, min_reprojection=False,
+                       auto_mask=False):
     """unsupervise.py:83-111.  ssim_weight > 0 (extension): the image term becomes a * DSSIM + (1 - a) * L1; the feature
-    term stays L1."""
+    term stays L1.  min_reprojection / auto_mask (extension): the image term takes the per-pixel minimum over the two
+    views, with the unwarped references competing under auto_mask; terms["automask"] is then the share of pixels won by
+    an identity candidate."""
+    counts = []
     R2, R1, L2 = batch["img_R2"], batch["img_R1"], batch["img_L2"]
     # unsupervise.py:92,95 (cat(R2, R1) done virtually) and :94 (intended: finest disparity)
     (_, T_2to1), disps = _side_by_side(lambda: pose_net((R2, R1)), lambda: depth_net(R2))
@@ -60,9 +70,13 @@ def unsupervise_losses(depth_net, pose_net, batch, feat_extractor=None, img_scal
     depth = reciprocal(inv_depth, depth_eps).squeeze(1)            # :99
     img_loss = LF.photometric_reconstruction_loss(R2, R1, L2, depth, T_2to1, batch["T_R2L"], batch["K"], batch["Kinv"],
                                                   img_scale=img_scale,   # :101 (0.004 * img applied inside the kernel)
-                                                  ssim_weight=ssim_weight, ssim_c1=ssim_c1, ssim_c2=ssim_c2)
+                                                  ssim_weight=ssim_weight, ssim_c1=ssim_c1, ssim_c2=ssim_c2,
+                                                  min_reprojection=min_reprojection, auto_mask=auto_mask,
+                                                  selection_counts=counts)
     smooth = LF.smooth_loss(depth.unsqueeze(1))                    # :102
     terms = {"img": img_loss.detach(), "smooth": smooth.detach()}
+    if auto_mask:
+        terms["automask"] = _identity_share(counts[0], 2)
     loss = img_loss + smooth_weight * smooth
     if feat_extractor is not None:
         b = R2.size(0)
@@ -91,20 +105,30 @@ def depth_only_losses(depth_net, batch, img_scale=0.004, smooth_weight=10.0, dep
 
 def train_sfm_losses(disp_net, pose_exp_net, batch, w1=1.0, w2=0.0, w3=0.1, smooth_factor=2.0,
                      rotation_mode="euler", padding_mode="zeros", feat_extractor=None, feat_weight=0.1,
-                     ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4):
-    """train.py:179-203.  ssim_weight > 0 (extension): the 4-scale photometric term becomes a * DSSIM + (1 - a) * L1.  feat_extractor: BASELINE.json configs[3] (cfg 4) adds the feature-reconstruction term of
+                     ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4, min_reprojection=False, auto_mask=False):
+    """train.py:179-203.  ssim_weight > 0 (extension): the 4-scale photometric term becomes a * DSSIM + (1 - a) * L1.
+    min_reprojection / auto_mask (extension): the image term takes the per-pixel minimum over the views (the unwarped
+    references competing under auto_mask) and no explainability mask, so w2 must be 0; terms["automask"] is the share of
+    finest-scale pixels won by an identity candidate.  feat_extractor: BASELINE.json configs[3] (cfg 4) adds the feature-reconstruction term of
     unsupervise.py:104-111 (single scale, finest depth, the network's two poses) to the 4-scale body."""
+    if min_reprojection and w2 > 0:
+        raise ValueError("min_reprojection leaves the explainability mask out of the photometric term: w2 must be 0")
     tgt = batch["img_R2"]
     refs = [batch["img_R1"], batch["img_L2"]] + list(batch.get("extra_refs", []))[: pose_exp_net.nb_ref_imgs - 2]
     (masks, pose), disparities = _side_by_side(lambda: pose_exp_net(tgt, refs), lambda: disp_net(tgt))   # train.py:187,189
     depth = [reciprocal(d, 0.0) for d in disparities]              # :188
-    l1 = LS.photometric_reconstruction_loss(tgt, refs, batch["K"], batch["Kinv"], depth, masks, pose,
+    counts = []
+    l1 = LS.photometric_reconstruction_loss(tgt, refs, batch["K"], batch["Kinv"], depth,
+                                            [None] * len(depth) if min_reprojection else masks, pose,
                                             rotation_mode, padding_mode, ssim_weight=ssim_weight, ssim_c1=ssim_c1,
-                                            ssim_c2=ssim_c2)                                       # :191
+                                            ssim_c2=ssim_c2, min_reprojection=min_reprojection, auto_mask=auto_mask,
+                                            selection_counts=counts)                               # :191
     l3 = LS.smooth_loss(depth, smooth_factor)                      # :200
     l4 = torch.nn.functional.mse_loss(pose[:, 1], batch["T_R2L"])  # :201  (24 floats: left to torch)
     loss = w1 * l1 + w3 * l3 + l4
     terms = {"photo": l1.detach(), "smooth": l3.detach(), "lr": l4.detach()}
+    if auto_mask:
+        terms["automask"] = _identity_share(counts[0], len(refs))
     if w2 > 0:
         l2 = LS.explainability_loss(masks)                         # :195-196
         loss = loss + w2 * l2

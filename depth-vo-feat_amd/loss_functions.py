@@ -9,7 +9,8 @@ from inverse_warp import inverse_warp, check_sizes  # noqa: F401  (re-exported l
 
 def photometric_reconstruction_loss(img_R2, img_R1, img_L2, depth, T_2to1, T_R2L, intrinsics, intrinsics_inv,
                                     rotation_mode='euler', padding_mode='zeros', align_corners=False, img_scale=1.0,
-                                    ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4):
+                                    ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4, min_reprojection=False, auto_mask=False,
+                                    selection_counts=None):
     """Temporal (img_R1 warped with T_2to1) + stereo (img_L2 warped with T_R2L) masked L1 against img_R2
     (reference loss_functions.py:7-20).  Works for images (C=3) and 32-channel feature maps alike; grads
     flow to depth, both poses and any image/feature input that requires them.
@@ -18,9 +19,24 @@ def photometric_reconstruction_loss(img_R2, img_R1, img_L2, depth, T_2to1, T_R2L
     scaled copies.
     ``ssim_weight`` (extension, default 0 = the reference's L1): a value a > 0 replaces |diff| by
     a * DSSIM + (1 - a) * |diff| (monodepth2 form; ``ssim_c1`` / ``ssim_c2`` must fit the range of img_scale * img).  The
-    reference has no SSIM: parity unpinned.  Composition of one inverse warp per view and dvf.ops.SsimL1LossFn."""
+    reference has no SSIM: parity unpinned.  Composition of one inverse warp per view and dvf.ops.SsimL1LossFn.
+    ``min_reprojection`` (extension, default off): the per-pixel MINIMUM over the two views of a * DSSIM + (1 - a) * L1
+    (a = ``ssim_weight``, 0 allowed) instead of their sum; with ``auto_mask`` the unwarped img_R1 / img_L2 compete too
+    (tests/minreproj_ref.py; dvf.ops.MinReprojLossFn).  ``selection_counts``: a list that receives the int32 [K+1] tensor of
+    pixels won by each candidate (temporal, stereo, then the two identities; last entry: no usable candidate)."""
     assert(intrinsics_inv.size() == intrinsics.size())
+    if auto_mask and not min_reprojection:
+        raise ValueError("auto_mask needs min_reprojection=True")
     flags = _L.geom_flags(rotation_mode, padding_mode, align_corners)
+    if min_reprojection:
+        from dvf.ops import InverseWarpFn, MinReprojLossFn
+        warped = [InverseWarpFn.apply(src, depth, T, intrinsics, intrinsics_inv, flags)
+                  for src, T in ((img_R1, T_2to1), (img_L2, T_R2L))]
+        cfg = (float(img_scale), float(ssim_weight), float(ssim_c1), float(ssim_c2), bool(auto_mask))
+        loss, _, counts = MinReprojLossFn.apply(img_R2, cfg, 2, *warped, *((img_R1, img_L2) if auto_mask else ()))
+        if selection_counts is not None:
+            selection_counts.append(counts)
+        return loss
     if ssim_weight > 0:
         from dvf.ops import InverseWarpFn, SsimL1LossFn
         cfg = (float(img_scale), float(ssim_weight), float(ssim_c1), float(ssim_c2), None)

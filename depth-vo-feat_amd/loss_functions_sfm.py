@@ -8,7 +8,8 @@ from dvf.ops import ExplainabilityLossFn, PhotoLossFn, SmoothLossFn
 
 def photometric_reconstruction_loss(tgt_img, ref_imgs, intrinsics, intrinsics_inv, depth, explainability_mask, pose,
                                     rotation_mode='euler', padding_mode='zeros', align_corners=False,
-                                    check_nan=False, ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4):
+                                    check_nan=False, ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4, min_reprojection=False,
+                                    auto_mask=False, selection_counts=None):
     """Sum over scales and reference views of the masked, explainability-weighted L1 between the target and
     the inverse-warped references (reference loss_functions_sfm.py:9-46).  One fused kernel per scale handles
     all views.  The reference's per-view NaN assert (:34) forces a device sync per view per scale; here it is
@@ -16,12 +17,22 @@ def photometric_reconstruction_loss(tgt_img, ref_imgs, intrinsics, intrinsics_in
     ``ssim_weight`` (extension, default 0 = the reference's L1): a value a > 0 replaces |diff| by
     a * DSSIM + (1 - a) * |diff| (monodepth2 form: 3x3 reflected windows, ``ssim_c1`` / ``ssim_c2`` for images in [-1, 1]).
     The reference has no SSIM, so parity of this term is unpinned.  It is a composition, not the fused kernel: per scale and
-    view one inverse warp materialises the warped image, then dvf.ops.SsimL1LossFn."""
+    view one inverse warp materialises the warped image, then dvf.ops.SsimL1LossFn.
+    ``min_reprojection`` (extension, default off): the appearance term a * DSSIM + (1 - a) * L1 (a = ``ssim_weight``, 0
+    allowed) is reduced per pixel by the MINIMUM over the views instead of their sum, and with ``auto_mask`` the unwarped
+    references compete as well, so a pixel that does not move between frames is won by an identity candidate and pulls on
+    no depth (definition: tests/minreproj_ref.py; dvf.ops.MinReprojLossFn, one call per scale over all views).  The
+    explainability mask is not part of this mode: every mask must be None.  ``selection_counts``: a list that receives, per
+    scale, the int32 [K+1] tensor of pixels won by each candidate (the last entry: no usable candidate)."""
+    if auto_mask and not min_reprojection:
+        raise ValueError("auto_mask needs min_reprojection=True")
     if type(explainability_mask) not in [tuple, list]:
         explainability_mask = [explainability_mask]
     if type(depth) not in [list, tuple]:
         depth = [depth]
     assert(pose.size(1) == len(ref_imgs))
+    if min_reprojection and any(m is not None for m in explainability_mask):
+        raise ValueError("min_reprojection does not take an explainability mask: pass None for every scale")
     flags = _L.geom_flags(rotation_mode, padding_mode, align_corners)
     pose_vb6 = pose.transpose(0, 1).contiguous()                        # [V, B, 6]
     loss = 0
@@ -33,6 +44,15 @@ def photometric_reconstruction_loss(tgt_img, ref_imgs, intrinsics, intrinsics_in
         refs_s = [area_downsample(r, (h, w)) for r in ref_imgs]          # :19
         k_s = torch.cat((intrinsics[:, 0:2] / downscale, intrinsics[:, 2:]), dim=1)               # :20
         kinv_s = torch.cat((intrinsics_inv[:, :, 0:2] * downscale, intrinsics_inv[:, :, 2:]), dim=2)   # :21
+        if min_reprojection:
+            from dvf.ops import InverseWarpFn, MinReprojLossFn
+            warped = [InverseWarpFn.apply(ref_s, d[:, 0], pose[:, v], k_s, kinv_s, flags) for v, ref_s in enumerate(refs_s)]
+            cfg = (1.0, float(ssim_weight), float(ssim_c1), float(ssim_c2), bool(auto_mask))
+            term, _, counts = MinReprojLossFn.apply(tgt_s, cfg, len(refs_s), *warped, *(refs_s if auto_mask else ()))
+            if selection_counts is not None:
+                selection_counts.append(counts)
+            loss = loss + term
+            continue
         if ssim_weight > 0:
             from dvf.ops import InverseWarpFn, SsimL1LossFn
             for v, ref_s in enumerate(refs_s):

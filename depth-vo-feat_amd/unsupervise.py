@@ -66,9 +66,10 @@ def main():
         n.to(args._device).train()
 
     def loss_fn(batch):
-        return unsupervise_losses(depth_net, odometry_net, batch, feat_extractor=feat, **cli.ssim_kwargs(args))
+        return unsupervise_losses(depth_net, odometry_net, batch, feat_extractor=feat, **cli.ssim_kwargs(args),
+                                  **cli.minreproj_kwargs(args))
 
-    terms = ["total", "img", "smooth"] + (["feat"] if feat is not None else [])
+    terms = ["total", "img", "smooth"] + (["feat"] if feat is not None else []) + (["automask"] if args.auto_mask else [])
     cli.run_training(args, nets, loss_fn, args.lr, (0.9, 0.999), args.weight_decay, terms, ckpts)
 
 

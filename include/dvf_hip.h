@@ -179,6 +179,35 @@ int dvf_ssim_loss_bwd(const float *tgt, const float *warped, const float *mask, 
                       float *g_warped, float *g_tgt, float *g_mask, int B, int C, int H, int W, float in_scale, float alpha,
                       float c1, float c2, void *stream);
 
+/* ---------------------------------------------------------------- per-pixel minimum reprojection + auto-mask (extension, opt-in)
+ * The second part of the monodepth2 appearance term; like SSIM there is NO reference call site, parity is unpinned and
+ * tests/minreproj_ref.py is the definition.  x = fl(in_scale * tgt) [B,C,H,W]; cands: HOST array of K device pointers to
+ * [B,C,H,W] images, used as y_k = fl(in_scale * cands[k]): the V warped references (outputs of dvf_inverse_warp_fwd),
+ * 1 <= V <= 4, then -- auto_mask != 0 -- the V unwarped references in the same order (K = V or 2V).  Per pixel p:
+ *   e_k(p) = (1/C) sum_c [alpha * dssim_c(x, y_k)(p) + (1 - alpha) * |x_c(p) - y_k,c(p)|]     (dssim as above; alpha = 0 allowed)
+ *   usable : a warped candidate unless it is exactly zero in all channels at p (no gradient); an identity candidate always
+ *   k*(p)  = the LOWEST index among the usable candidates that attain min_k e_k(p): a tie goes to a warped view before an
+ *            identity one, there is no tie-break noise; "none" when no candidate is usable
+ *   loss_out[0] (+)= sum_p e_k*(p)(p) / (B H W)   (pixels with no usable candidate add 0 and stay in the denominator; the
+ *            value of a winning identity candidate is included, it is constant with respect to the networks)
+ * select: uint8 [B,H,W], k*(p), 255 = none.  counts: K+1 int32, the number of pixels per selection, the last one "none".
+ * partials: workspace >= dvf_minreproj_partials_floats(B,H,W,K) floats.  Loss and counts are reduced from per-block
+ *   partials in a fixed order, without atomics: both are bit-reproducible.
+ * Backward (one launch, gather form, no atomics): the selection is piecewise constant; g_warped[k] (HOST array of V device
+ *   pointers, the array or any entry may be NULL) collects the windows q with k*(q) = k, g_tgt (may be NULL) the selected
+ *   candidate of every window, identity candidates included; identity sources get no gradient.  grad_loss is a DEVICE
+ *   scalar; every element of a given output is written exactly once, nothing needs zeroing.  The clamp gate of dssim
+ *   behaves as in dvf_ssim_loss_bwd.
+ * DVF_ERR_INVALID_ARG for null pointers, V outside 1..4, H or W < 3, C*H*W >= 2^31, B > 65535.  No allocation, no
+ * synchronisation: the calls can be captured in a HIP graph. */
+int64_t dvf_minreproj_partials_floats(int B, int H, int W, int K);
+int dvf_minreproj_fwd(const float *tgt, const float *const *cands, int V, int auto_mask, float *loss_out, uint8_t *select,
+                      int32_t *counts, float *partials, int B, int C, int H, int W, float in_scale, float alpha, float c1, float c2,
+                      int accumulate, void *stream);
+int dvf_minreproj_bwd(const float *tgt, const float *const *cands, int V, int auto_mask, const uint8_t *select,
+                      const float *grad_loss, float *g_tgt, float *const *g_warped, int B, int C, int H, int W, float in_scale,
+                      float alpha, float c1, float c2, void *stream);
+
 /* ---------------------------------------------------------------- smoothness loss
  * Replaces one map of smooth_loss (loss_functions.py:23-41 ; loss_functions_sfm.py:59-77):
  * weight * (mean|dx2| + mean|dxdy| + mean|dydx| + mean|dy2|) of a [N,H,W] stack of planes (N = B*C).
