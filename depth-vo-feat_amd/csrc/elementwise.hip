@@ -1,21 +1,10 @@
 // Memory-bound helpers of the training step: bilinear x2 upsampling (DispNetS disparity pyramid),
 // reciprocal (disparity -> depth), spatial mean (pose head), area down-sampling (sfm image pyramid),
 // bilinear x0.5 (FeatExtractor image pyramid) and the fused multi-tensor Adam update.
+#include "bilinear_src.h"
 #include "dvf_common.h"
 
 namespace {
-
-// aten area_pixel_compute_source_index(scale, dst, align_corners=False, cubic=False)
-__device__ __forceinline__ void up_src(int dst, float scale, int in_size, int &i0, int &i1, float &lam) {
-    float src = scale * ((float)dst + 0.5f) - 0.5f;
-    if (src < 0.f) src = 0.f;
-    i0 = (int)src;                       // floor: src >= 0
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-    lam = src - (float)i0;
-    if (lam < 0.f) lam = 0.f;
-    if (lam > 1.f) lam = 1.f;
-}
 
 // out[n][c][Y][X] for Y < OH, X < OW (OH <= 2H: the crop of crop_like is folded in).  DispNetS.py:115
 __global__ void resize_bilinear_fwd_kernel(const float *in, float *out, int H, int W, int OH, int OW, float sy, float sx,

@@ -537,33 +537,6 @@ __global__ __launch_bounds__(256) void photo_bwd_kernel(PhotoArgs a) {
     }
 }
 
-// Second stage of the pose-gradient reduction: pose_ws[(v*B+b)*12 + k] = sum over the blocks of image b, fixed order
-// (1008 threads = 84 strided partial sums per value, then a fixed-order sum of the 84).
-__global__ __launch_bounds__(1024) void pose_sum_kernel(const float *part, float *pose_ws, int V, int B, int blocks_per_img) {
-    __shared__ float red[84][12];
-    const int v = blockIdx.x / B, b = blockIdx.x - v * B;
-    const int t = threadIdx.x;
-    if (t < 1008) {
-        const int k = t % 12, j = t / 12;
-        const float *p = part + ((int64_t)b * blocks_per_img * V + v) * 12 + k;
-        float s0 = 0.f, s1 = 0.f;
-        int i = j;
-        for (; i + 84 < blocks_per_img; i += 168) {          // two loads in flight
-            const float a0 = p[(int64_t)i * V * 12], a1 = p[(int64_t)(i + 84) * V * 12];
-            s0 += a0;
-            s1 += a1;
-        }
-        if (i < blocks_per_img) s0 += p[(int64_t)i * V * 12];
-        red[j][k] = s0 + s1;
-    }
-    __syncthreads();
-    if (t < 12) {
-        float s = 0.f;
-        for (int j = 0; j < 84; ++j) s += red[j][t];
-        pose_ws[((int64_t)v * B + b) * 12 + t] = s;
-    }
-}
-
 inline dim3 photo_grid(int B, int H, int W) { return dim3((W + TX - 1) / TX, (H + TY - 1) / TY, B); }
 inline int photo_tile_floats(int C) { const int t = (C < PT_CC ? C : PT_CC) * PT_CAP; return t < PT_MIN_TILE ? PT_MIN_TILE : t; }
 

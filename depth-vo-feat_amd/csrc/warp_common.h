@@ -274,6 +274,34 @@ __device__ __forceinline__ void reduce_pose_partials(float (&acc)[NV][12], int V
 }
 
 
+// Second stage of the pose-gradient reduction: pose_ws[(v*B+b)*12 + k] = sum over the blocks of image b, fixed order
+// (shared by the fused photometric backward, V views per block record, and the ordered inverse-warp backward, V = 1;
+// 1008 threads = 84 strided partial sums per value, then a fixed-order sum of the 84).
+static __global__ __launch_bounds__(1024) void pose_sum_kernel(const float *part, float *pose_ws, int V, int B, int blocks_per_img) {
+    __shared__ float red[84][12];
+    const int v = blockIdx.x / B, b = blockIdx.x - v * B;
+    const int t = threadIdx.x;
+    if (t < 1008) {
+        const int k = t % 12, j = t / 12;
+        const float *p = part + ((int64_t)b * blocks_per_img * V + v) * 12 + k;
+        float s0 = 0.f, s1 = 0.f;
+        int i = j;
+        for (; i + 84 < blocks_per_img; i += 168) {          // two loads in flight
+            const float a0 = p[(int64_t)i * V * 12], a1 = p[(int64_t)(i + 84) * V * 12];
+            s0 += a0;
+            s1 += a1;
+        }
+        if (i < blocks_per_img) s0 += p[(int64_t)i * V * 12];
+        red[j][k] = s0 + s1;
+    }
+    __syncthreads();
+    if (t < 12) {
+        float s = 0.f;
+        for (int j = 0; j < 84; ++j) s += red[j][t];
+        pose_ws[((int64_t)v * B + b) * 12 + t] = s;
+    }
+}
+
 // pose_ws[(v*B+b)*12] = (g_t[3], g_R[9]) -> g_pose[(v*B+b)*6] through d R / d (rx,ry,rz).
 static __global__ void pose_finalize_kernel(const float *pose, const float *ws, float *g_pose, int n, uint32_t quat) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

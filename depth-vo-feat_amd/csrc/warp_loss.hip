@@ -23,6 +23,8 @@ struct WarpArgs {
     float *out, *g_img, *g_depth, *pose_ws;
     int B, C, H, W;
     uint32_t quat;
+    float *pose_part;      // BWD: NULL = the blocks add their [R|t] partials into pose_ws with float atomics; else one record of
+                           // 12 floats per block, summed in block order by pose_sum_kernel
 };
 
 template <bool BORDER, bool ALIGN, bool PIX, bool BWD>
@@ -92,7 +94,10 @@ __global__ __launch_bounds__(256) void warp_kernel(WarpArgs a) {
             pacc[0][9] = gyz * cx; pacc[0][10] = gyz * cy; pacc[0][11] = gyz * cz;
         }
     }
-    if (BWD && a.pose_ws) reduce_pose_partials<1>(pacc, 1, a.B, b, a.pose_ws, red);
+    if (BWD && a.pose_ws) {
+        float *part = a.pose_part ? a.pose_part + (((int64_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 12 : nullptr;
+        reduce_pose_partials<1>(pacc, 1, a.B, b, a.pose_ws, red, part);
+    }
 }
 
 // ------------------------------------------------------------------ smoothness loss
@@ -354,28 +359,55 @@ int dvf_inverse_warp_fwd(const float *img, const float *depth, const float *pose
     });
 }
 
-int dvf_inverse_warp_bwd(const float *img, const float *depth, const float *pose, const float *K, const float *Kinv,
-                         const float *grad_out, float *g_img, float *g_depth, float *g_pose, float *pose_ws, int B,
-                         int C, int H, int W, uint32_t flags, void *stream) {
+static int inverse_warp_bwd(const float *img, const float *depth, const float *pose, const float *K, const float *Kinv,
+                            const float *grad_out, float *g_img, float *g_depth, float *g_pose, float *pose_ws,
+                            float *pose_part, int B, int C, int H, int W, uint32_t flags, void *stream) {
     if (!img || !depth || !pose || !K || !Kinv || !grad_out || B <= 0 || C <= 0 || H < 2 || W < 2 || B > 65535)
         return DVF_ERR_INVALID_ARG;
     if (g_pose && !pose_ws) return DVF_ERR_INVALID_ARG;
     hipStream_t st = dvf_stream(stream);
-    if (g_pose && hipMemsetAsync(pose_ws, 0, sizeof(float) * 12 * B, st) != hipSuccess) return DVF_ERR_LAUNCH;
+    const bool ordered = g_pose && pose_part;
+    if (g_pose && !ordered && hipMemsetAsync(pose_ws, 0, sizeof(float) * 12 * B, st) != hipSuccess) return DVF_ERR_LAUNCH;
     WarpArgs a{img, depth, pose, K, Kinv, grad_out, nullptr, g_img, g_depth, g_pose ? pose_ws : nullptr,
-               B, C, H, W, rot_mode(flags)};
+               B, C, H, W, rot_mode(flags), ordered ? pose_part : nullptr};
+    const dim3 grid = pix_grid(B, H, W);
     const int rc = dispatch_mode(flags, [&](auto border, auto align, auto pix) {
         warp_kernel<decltype(border)::value, decltype(align)::value, decltype(pix)::value, true>
-            <<<pix_grid(B, H, W), dim3(TX, TY), 0, st>>>(a);
+            <<<grid, dim3(TX, TY), 0, st>>>(a);
         DVF_LAUNCH_CHECK();
         return DVF_OK;
     });
     if (rc != DVF_OK) return rc;
     if (g_pose) {
+        if (ordered) {
+            pose_sum_kernel<<<B, 1024, 0, st>>>(pose_part, pose_ws, 1, B, (int)(grid.x * grid.y));
+            DVF_LAUNCH_CHECK();
+        }
         pose_finalize_kernel<<<(B + 63) / 64, 64, 0, st>>>(pose, pose_ws, g_pose, B, rot_mode(flags));
         DVF_LAUNCH_CHECK();
     }
     return DVF_OK;
+}
+
+int dvf_inverse_warp_bwd(const float *img, const float *depth, const float *pose, const float *K, const float *Kinv,
+                         const float *grad_out, float *g_img, float *g_depth, float *g_pose, float *pose_ws, int B,
+                         int C, int H, int W, uint32_t flags, void *stream) {
+    return inverse_warp_bwd(img, depth, pose, K, Kinv, grad_out, g_img, g_depth, g_pose, pose_ws, nullptr, B, C, H, W, flags,
+                            stream);
+}
+
+int64_t dvf_inverse_warp_ordered_ws_floats(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    const dim3 g = pix_grid(B, H, W);
+    return (int64_t)g.x * g.y * g.z * 12 + (int64_t)B * 12;
+}
+
+int dvf_inverse_warp_bwd_ordered(const float *img, const float *depth, const float *pose, const float *K, const float *Kinv,
+                                 const float *grad_out, float *g_img, float *g_depth, float *g_pose, float *ws, int B, int C,
+                                 int H, int W, uint32_t flags, void *stream) {
+    if (g_pose && !ws) return DVF_ERR_INVALID_ARG;
+    return inverse_warp_bwd(img, depth, pose, K, Kinv, grad_out, g_img, g_depth, g_pose, ws, ws ? ws + (int64_t)B * 12 : nullptr,
+                            B, C, H, W, flags, stream);
 }
 
 int dvf_pose_vec2mat_fwd(const float *pose, float *out, int n, uint32_t flags, void *stream) {

@@ -43,6 +43,11 @@ def add_common_flags(parser):
     g.add_argument("--auto-mask", action="store_true",
                    help="with --min-reprojection: the unwarped reference views compete in the minimum, so pixels that do not "
                         "move between frames are won by an identity candidate; the logged 'automask' is their share")
+    g.add_argument("--full-res-multiscale", action="store_true",
+                   help="train.py only: every scale's disparity (and explainability mask) is upsampled bilinearly to the input "
+                        "resolution and its photometric term is taken there, against the full-resolution images (monodepth2 "
+                        "form), instead of at the scale's own resolution; smoothness and the mask regulariser stay at the "
+                        "native scales.  Not in the reference: parity unpinned.  The single-scale entry points refuse it")
     g.add_argument("--reference-stereo-pose", action="store_true",
                    help="feed the dataset's T_R2L file vector (0,0,0,Tx,0,0) unchanged into pose_vec2mat / the stereo-pose "
                         "MSE target, exactly as the reference does (unsupervise.py:101, train.py:201); default: convert it "
@@ -57,6 +62,21 @@ def ssim_kwargs(args):
 def minreproj_kwargs(args):
     """The --min-reprojection / --auto-mask flags as keywords of the step bodies (dvf/steps.py)."""
     return {"min_reprojection": args.min_reprojection, "auto_mask": args.auto_mask}
+
+
+FULLRES_SINGLE_SCALE = ("--full-res-multiscale needs a multi-scale loss: this entry point has a single scale, already at the "
+                        "input resolution (use train.py)")
+
+
+def fullres_kwargs(args, multiscale=True):
+    """The --full-res-multiscale flag as a keyword of the multi-scale step body (dvf/steps.py::train_sfm_losses).  An entry
+    point whose loss has one scale calls this with ``multiscale=False``: it gets no keyword, and the flag raises ValueError
+    there instead of being ignored."""
+    if not multiscale:
+        if args.full_res_multiscale:
+            raise ValueError(FULLRES_SINGLE_SCALE)
+        return {}
+    return {"full_res_multiscale": args.full_res_multiscale}
 
 
 def init_distributed():

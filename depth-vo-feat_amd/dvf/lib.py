@@ -45,6 +45,8 @@ SIGNATURES = {
     "dvf_inverse_warp_fwd": (c_i, [c_fp] * 6 + [c_i] * 4 + [c_u32, c_fp]),
     "dvf_inverse_warp_bwd": (c_i, [c_fp] * 10 + [c_i] * 4 + [c_u32, c_fp]),
     "dvf_pose_ws_floats": (c_i64, [c_i, c_i]),
+    "dvf_inverse_warp_ordered_ws_floats": (c_i64, [c_i] * 3),
+    "dvf_inverse_warp_bwd_ordered": (c_i, [c_fp] * 10 + [c_i] * 4 + [c_u32, c_fp]),
     "dvf_pose_vec2mat_fwd": (c_i, [c_fp, c_fp, c_i, c_u32, c_fp]),
     "dvf_pose_vec2mat_bwd": (c_i, [c_fp] * 4 + [c_i, c_u32, c_fp]),
     "dvf_pixel2cam_fwd": (c_i, [c_fp] * 3 + [c_i] * 3 + [c_fp]),
@@ -81,6 +83,8 @@ SIGNATURES = {
     "dvf_act_bwd_ws_floats": (c_i64, [c_i, c_i, c_i]),
     "dvf_resize_bilinear_fwd": (c_i, [c_fp, c_fp] + [c_i] * 5 + [c_f, c_f, c_fp]),
     "dvf_upsample2x_bwd": (c_i, [c_fp, c_fp] + [c_i] * 5 + [c_fp]),
+    "dvf_upsample_int_fwd": (c_i, [c_fp, c_fp] + [c_i] * 5 + [c_f, c_fp]),
+    "dvf_upsample_int_bwd": (c_i, [c_fp] * 3 + [c_i] * 5 + [c_fp]),
     "dvf_recip_fwd": (c_i, [c_fp, c_fp, c_f, c_i64, c_fp]),
     "dvf_recip_bwd": (c_i, [c_fp, c_fp, c_fp, c_i64, c_fp]),
     "dvf_spatial_mean_fwd": (c_i, [c_fp, c_fp, c_i, c_i, c_f, c_fp]),

@@ -40,11 +40,15 @@ class InverseWarpFn(torch.autograd.Function):
         g_img = torch.zeros_like(img) if need_img else None
         g_depth = torch.empty_like(depth) if need_depth else None
         g_pose = torch.empty_like(pose) if need_pose else None
-        ws = torch.empty(int(L.lib().dvf_pose_ws_floats(1, B)), device=img.device) if need_pose else None
-        L.check(L.lib().dvf_inverse_warp_bwd(L.dev(img), L.dev(depth), L.dev(pose), L.dev(K), L.dev(Kinv),
-                                             L.dev(_f32c(gout), "grad_out"), L.dev(g_img), L.dev(g_depth),
-                                             L.dev(g_pose), L.dev(ws), B, C, H, W, ctx.flags, L.stream()),
-                "dvf_inverse_warp_bwd")
+        lib = L.lib()
+        # deterministic mode: the pose gradient's per-block partials go through a scratch and are added in block order
+        ordered = _conv.DETERMINISTIC and need_pose
+        bwd, what = (lib.dvf_inverse_warp_bwd_ordered, "dvf_inverse_warp_bwd_ordered") if ordered else \
+            (lib.dvf_inverse_warp_bwd, "dvf_inverse_warp_bwd")
+        ws_floats = lib.dvf_inverse_warp_ordered_ws_floats(B, H, W) if ordered else lib.dvf_pose_ws_floats(1, B)
+        ws = torch.empty(int(ws_floats), device=img.device) if need_pose else None
+        L.check(bwd(L.dev(img), L.dev(depth), L.dev(pose), L.dev(K), L.dev(Kinv), L.dev(_f32c(gout), "grad_out"), L.dev(g_img),
+                    L.dev(g_depth), L.dev(g_pose), L.dev(ws), B, C, H, W, ctx.flags, L.stream()), what)
         return g_img, g_depth, g_pose, None, None, None
 
 
@@ -230,6 +234,40 @@ class MinReprojLossFn(torch.autograd.Function):
                                               L.dev(_f32c(gloss).reshape(1), "grad_loss"), L.dev(g_tgt), L.ptr_array(g_warped),
                                               B, C, H, W, in_scale, alpha, c1, c2, L.stream()), "dvf_minreproj_bwd")
         return (g_tgt, None, None, *g_warped, *([None] * (len(cands) - V)))
+
+
+class UpsampleIntFn(torch.autograd.Function):
+    """Bilinear upsampling of x [B,C,H,W] by an integer ``factor`` (2, 4 or 8; F.interpolate(mode='bilinear',
+    align_corners=False)), with ``recip_eps`` a float followed in the same pass by 1 / (. + recip_eps): a coarse disparity
+    becomes a full-resolution depth and the upsampled disparity is never stored (csrc/upsample.hip; build-side extension,
+    definition tests/fullres_ref.py).  ``recip_eps=None``: plain upsampling (explainability masks).  The backward is the
+    exact transpose in gather form, bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, x, factor, recip_eps=None):
+        x = _f32c(x)
+        if x.dim() != 4:
+            raise ValueError(f"expected a [B,C,H,W] map, got {tuple(x.shape)}")
+        B, C, H, W = x.shape
+        factor, recip = int(factor), recip_eps is not None
+        out = torch.empty((B, C, factor * H, factor * W), device=x.device, dtype=torch.float32)
+        with L.timed("upsample_int_fwd", 0.0, 4.0 * (x.numel() + out.numel())):
+            L.check(L.lib().dvf_upsample_int_fwd(L.dev(x, "input"), L.dev(out), B * C, H, W, factor, int(recip),
+                                                 float(recip_eps) if recip else 0.0, L.stream()), "dvf_upsample_int_fwd")
+        if recip:
+            ctx.save_for_backward(out)
+        ctx.cfg = (B, C, H, W, factor, recip)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        B, C, H, W, factor, recip = ctx.cfg
+        out = ctx.saved_tensors[0] if recip else None
+        gin = torch.empty((B, C, H, W), device=gout.device, dtype=torch.float32)
+        with L.timed("upsample_int_bwd", 0.0, 4.0 * (gin.numel() + gout.numel() * (2 if recip else 1))):
+            L.check(L.lib().dvf_upsample_int_bwd(L.dev(_f32c(gout), "grad_out"), L.dev(out), L.dev(gin), B * C, H, W, factor,
+                                                 int(recip), L.stream()), "dvf_upsample_int_bwd")
+        return gin, None, None
 
 
 class SmoothLossFn(torch.autograd.Function):

@@ -105,12 +105,18 @@ def depth_only_losses(depth_net, batch, img_scale=0.004, smooth_weight=10.0, dep
 
 def train_sfm_losses(disp_net, pose_exp_net, batch, w1=1.0, w2=0.0, w3=0.1, smooth_factor=2.0,
                      rotation_mode="euler", padding_mode="zeros", feat_extractor=None, feat_weight=0.1,
-                     ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4, min_reprojection=False, auto_mask=False):
+                     ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4, min_reprojection=False, auto_mask=False,
+                     full_res_multiscale=False):
     """train.py:179-203.  ssim_weight > 0 (extension): the 4-scale photometric term becomes a * DSSIM + (1 - a) * L1.
     min_reprojection / auto_mask (extension): the image term takes the per-pixel minimum over the views (the unwarped
     references competing under auto_mask) and no explainability mask, so w2 must be 0; terms["automask"] is the share of
     finest-scale pixels won by an identity candidate.  feat_extractor: BASELINE.json configs[3] (cfg 4) adds the feature-reconstruction term of
-    unsupervise.py:104-111 (single scale, finest depth, the network's two poses) to the 4-scale body."""
+    unsupervise.py:104-111 (single scale, finest depth, the network's two poses) to the 4-scale body.
+    full_res_multiscale (extension, monodepth2 form): every scale's disparity (and explainability mask) is upsampled
+    bilinearly to the input resolution, turned into depth there (one fused pass, LS.full_resolution) and the photometric term
+    of every scale warps the full-resolution references against the full-resolution target; gradients reach the coarse
+    disparities and masks.  Smoothness, the explainability regulariser, the stereo-pose MSE and the feature term stay on the
+    native-scale maps; terms["automask"] is still the finest scale's share.  Off: nothing changes."""
     if min_reprojection and w2 > 0:
         raise ValueError("min_reprojection leaves the explainability mask out of the photometric term: w2 must be 0")
     tgt = batch["img_R2"]
@@ -118,8 +124,14 @@ def train_sfm_losses(disp_net, pose_exp_net, batch, w1=1.0, w2=0.0, w3=0.1, smoo
     (masks, pose), disparities = _side_by_side(lambda: pose_exp_net(tgt, refs), lambda: disp_net(tgt))   # train.py:187,189
     depth = [reciprocal(d, 0.0) for d in disparities]              # :188
     counts = []
-    l1 = LS.photometric_reconstruction_loss(tgt, refs, batch["K"], batch["Kinv"], depth,
-                                            [None] * len(depth) if min_reprojection else masks, pose,
+    photo_depth, photo_masks = depth, masks
+    if full_res_multiscale:
+        hw = tgt.shape[2:]
+        photo_depth = LS.full_resolution(disparities, hw, recip_eps=0.0)
+        if not min_reprojection:
+            photo_masks = LS.full_resolution(masks, hw)
+    l1 = LS.photometric_reconstruction_loss(tgt, refs, batch["K"], batch["Kinv"], photo_depth,
+                                            [None] * len(depth) if min_reprojection else photo_masks, pose,
                                             rotation_mode, padding_mode, ssim_weight=ssim_weight, ssim_c1=ssim_c1,
                                             ssim_c2=ssim_c2, min_reprojection=min_reprojection, auto_mask=auto_mask,
                                             selection_counts=counts)                               # :191

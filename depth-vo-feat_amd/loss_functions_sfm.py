@@ -2,8 +2,8 @@
 import torch
 
 from dvf import lib as _L
-from dvf.conv import area_downsample
-from dvf.ops import ExplainabilityLossFn, PhotoLossFn, SmoothLossFn
+from dvf.conv import area_downsample, reciprocal
+from dvf.ops import ExplainabilityLossFn, PhotoLossFn, SmoothLossFn, UpsampleIntFn
 
 
 def photometric_reconstruction_loss(tgt_img, ref_imgs, intrinsics, intrinsics_inv, depth, explainability_mask, pose,
@@ -23,7 +23,10 @@ def photometric_reconstruction_loss(tgt_img, ref_imgs, intrinsics, intrinsics_in
     references compete as well, so a pixel that does not move between frames is won by an identity candidate and pulls on
     no depth (definition: tests/minreproj_ref.py; dvf.ops.MinReprojLossFn, one call per scale over all views).  The
     explainability mask is not part of this mode: every mask must be None.  ``selection_counts``: a list that receives, per
-    scale, the int32 [K+1] tensor of pixels won by each candidate (the last entry: no usable candidate)."""
+    scale, the int32 [K+1] tensor of pixels won by each candidate (the last entry: no usable candidate).
+    Full-resolution multi-scale sampling (extension, monodepth2 form) needs no keyword here: ``downscale`` comes from each
+    depth map's own size and ``area_downsample`` returns its input when the sizes agree, so a list of depths (and masks)
+    that ``full_resolution`` brought to the input resolution runs every mode above at that resolution for every scale."""
     if auto_mask and not min_reprojection:
         raise ValueError("auto_mask needs min_reprojection=True")
     if type(explainability_mask) not in [tuple, list]:
@@ -64,6 +67,32 @@ def photometric_reconstruction_loss(tgt_img, ref_imgs, intrinsics, intrinsics_in
     if check_nan:
         assert((loss == loss).item() == 1)
     return loss
+
+
+def full_resolution(maps, out_hw, recip_eps=None):
+    """The maps of a coarse-to-fine list brought to ``out_hw`` = (H, W) for full-resolution multi-scale sampling (extension;
+    definition tests/fullres_ref.py): every [B,C,h,w] map with H / h = W / w in {1, 2, 4, 8} is upsampled bilinearly
+    (align_corners=False) by dvf.ops.UpsampleIntFn; with ``recip_eps`` a float the result is 1 / (upsampled + recip_eps),
+    disparity -> depth, fused into the same pass.  A map already at (H, W) is returned as it is (through ``reciprocal``
+    with ``recip_eps``).  Gradients reach the coarse maps.  Any other size ratio raises ValueError.  Returns a list."""
+    H, W = int(out_hw[0]), int(out_hw[1])
+    if type(maps) not in [tuple, list]:
+        maps = [maps]
+    factors = []
+    for m in maps:                       # every size is checked before the first kernel runs
+        h, w = m.shape[2:]
+        f = H // h if h > 0 else 0
+        if m.dim() != 4 or f not in (1, 2, 4, 8) or (f * h, f * w) != (H, W):
+            raise ValueError(f"full_resolution: a map of size {tuple(m.shape)} does not reach {(H, W)} by a factor of 1, 2, 4 "
+                             f"or 8 in both axes")
+        factors.append(f)
+    out = []
+    for m, f in zip(maps, factors):
+        if f == 1:
+            out.append(m if recip_eps is None else reciprocal(m, recip_eps))
+        else:
+            out.append(UpsampleIntFn.apply(m, f, None if recip_eps is None else float(recip_eps)))
+    return out
 
 
 def explainability_loss(mask):

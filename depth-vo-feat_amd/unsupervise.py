@@ -42,6 +42,7 @@ cli.add_common_flags(parser)
 
 def main():
     args = parser.parse_args()
+    cli.fullres_kwargs(args, multiscale=False)            # one scale here: --full-res-multiscale raises instead of doing nothing
     args._rank, args._world, args._device = cli.init_distributed()
     torch.manual_seed(args.seed)
     depth_net, odometry_net = DispNetS(), PoseExpNet(output_exp=True)

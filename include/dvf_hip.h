@@ -81,6 +81,15 @@ int dvf_inverse_warp_bwd(const float *img, const float *depth, const float *pose
                          float *g_pose, float *pose_ws, int B, int C, int H, int W, uint32_t flags,
                          void *stream);
 int64_t dvf_pose_ws_floats(int V, int B);
+/* The same backward with the pose gradient summed in a FIXED order (deterministic mode): every block stores its [R|t]
+ * partial and one pass adds them in block order, instead of float atomics in order of arrival -- g_pose is then
+ * bit-reproducible from run to run like g_depth (g_img stays a scatter-add).  ws: >= dvf_inverse_warp_ordered_ws_floats(B, H, W)
+ * floats, contents irrelevant, nothing needs zeroing.  Build-side addition: the reference's autograd has no such choice. */
+int64_t dvf_inverse_warp_ordered_ws_floats(int B, int H, int W);
+int dvf_inverse_warp_bwd_ordered(const float *img, const float *depth, const float *pose, const float *K,
+                                 const float *Kinv, const float *grad_out, float *g_img, float *g_depth,
+                                 float *g_pose, float *ws, int B, int C, int H, int W, uint32_t flags,
+                                 void *stream);
 
 /* ---------------------------------------------------------------- stand-alone geometry helpers
  * The public building blocks of inverse_warp.py, for callers that use them directly (the fused kernels above do
@@ -304,6 +313,21 @@ int dvf_resize_bilinear_fwd(const float *in, float *out, int planes, int H, int 
                             float scale_w, void *stream);
 /* backward of the x2 case (gather form, no atomics): gout [planes,OH,OW] -> gin [planes,H,W] */
 int dvf_upsample2x_bwd(const float *gout, float *gin, int planes, int H, int W, int OH, int OW, void *stream);
+/* Integer-factor bilinear upsampling to the input resolution, optionally fused with the disparity -> depth reciprocal:
+ * the full-resolution multi-scale mode of the photometric losses.  Build-side EXTENSION: the reference has no such mode and
+ * there is no reference call site; parity is unpinned and tests/fullres_ref.py is the definition.
+ *   in [planes,H,W] -> out [planes,factor*H,factor*W] = F.interpolate(in, (factor*H, factor*W), mode='bilinear',
+ *   align_corners=False): src = (dst + 0.5) / factor - 0.5 clamped at 0, the upper tap clamped to the last row / column;
+ *   recip != 0: out = 1 / (that + eps) in the same pass (the upsampled disparity is never stored).  factor is 2, 4 or 8.
+ * Backward: the exact transpose, gin [planes,H,W] from gout [planes,factor*H,factor*W]; with recip != 0 gout is first
+ *   multiplied by -out^2, `out` being the forward's output (NULL allowed when recip == 0).  Gather form, separable (a row
+ *   pass into LDS, then a column pass), every sum in a fixed order and no atomics: bit-reproducible; gin is written once.
+ * Checked on the host before anything is launched: DVF_ERR_INVALID_ARG for a null pointer, a non-positive size or
+ *   planes * factor*H * factor*W >= 2^31 (the kernels index fine pixels in 32 bits); DVF_ERR_UNSUPPORTED for another factor. */
+int dvf_upsample_int_fwd(const float *in, float *out, int planes, int H, int W, int factor, int recip, float eps,
+                         void *stream);
+int dvf_upsample_int_bwd(const float *gout, const float *out, float *gin, int planes, int H, int W, int factor, int recip,
+                         void *stream);
 /* y = 1 / (x + eps)  (train.py:188 eps=0; unsupervise.py:99 eps=1e-4) and its backward gx = -gy * y^2 */
 int dvf_recip_fwd(const float *x, float *y, float eps, int64_t n, void *stream);
 int dvf_recip_bwd(const float *gy, const float *y, float *gx, int64_t n, void *stream);
