@@ -38,6 +38,15 @@ def test_null_arguments_are_rejected_without_touching_the_gpu():
     assert lib.dvf_smooth_loss_fwd(None, None, None, 1, 8, 8, 1.0, 0, None) == -1
 
 
+def test_one_column_images_are_rejected_by_the_sampler():
+    """W >= 2 and H >= 2 are the host's checks (the tap pair (xb, xb+1) must fit a row); pointers are not dereferenced."""
+    import ctypes
+    lib = L.lib()
+    fake = ctypes.c_void_p(0x1000)
+    assert lib.dvf_inverse_warp_fwd(fake, fake, fake, fake, fake, fake, 1, 3, 8, 1, 0, None) == -1
+    assert lib.dvf_inverse_warp_fwd(fake, fake, fake, fake, fake, fake, 1, 3, 1, 8, 0, None) == -1
+
+
 def test_product_refuses_cpu_tensors():
     """The product path has no CPU fallback: a CPU tensor must raise, not silently run elsewhere."""
     import torch
