@@ -48,6 +48,12 @@ def add_common_flags(parser):
                         "resolution and its photometric term is taken there, against the full-resolution images (monodepth2 "
                         "form), instead of at the scale's own resolution; smoothness and the mask regulariser stay at the "
                         "native scales.  Not in the reference: parity unpinned.  The single-scale entry points refuse it")
+    g.add_argument("--normalized-smoothness", action="store_true",
+                   help="the smoothness term becomes the edge-aware first-order smoothness of the mean-normalised disparity, "
+                        "against the target image (monodepth2 form), instead of the second-order smoothness of depth; it keeps "
+                        "the entry point's smoothness weight, which was chosen for the other term: monodepth2 uses 1e-3, so "
+                        "train.py -s 0.001, unsupervise.py / unsupervise_dvo.py --smooth-weight 0.001.  Not in the reference: "
+                        "parity unpinned, tests/normsmooth_ref.py is the definition")
     g.add_argument("--reference-stereo-pose", action="store_true",
                    help="feed the dataset's T_R2L file vector (0,0,0,Tx,0,0) unchanged into pose_vec2mat / the stereo-pose "
                         "MSE target, exactly as the reference does (unsupervise.py:101, train.py:201); default: convert it "
@@ -62,6 +68,11 @@ def ssim_kwargs(args):
 def minreproj_kwargs(args):
     """The --min-reprojection / --auto-mask flags as keywords of the step bodies (dvf/steps.py)."""
     return {"min_reprojection": args.min_reprojection, "auto_mask": args.auto_mask}
+
+
+def normsmooth_kwargs(args):
+    """The --normalized-smoothness flag as a keyword of the step bodies (dvf/steps.py)."""
+    return {"normalized_smoothness": args.normalized_smoothness}
 
 
 FULLRES_SINGLE_SCALE = ("--full-res-multiscale needs a multi-scale loss: this entry point has a single scale, already at the "

@@ -67,6 +67,9 @@ SIGNATURES = {
     "dvf_minreproj_partials_floats": (c_i64, [c_i] * 4),
     "dvf_minreproj_fwd": (c_i, [c_fp, c_pp, c_i, c_i] + [c_fp] * 4 + [c_i] * 4 + [c_f] * 4 + [c_i, c_fp]),
     "dvf_minreproj_bwd": (c_i, [c_fp, c_pp, c_i, c_i, c_fp, c_fp, c_fp, c_pp] + [c_i] * 4 + [c_f] * 4 + [c_fp]),
+    "dvf_norm_smooth_partials_floats": (c_i64, [c_i] * 3),
+    "dvf_norm_smooth_fwd": (c_i, [c_fp] * 5 + [c_i] * 4 + [c_f, c_f, c_f, c_i, c_fp]),
+    "dvf_norm_smooth_bwd": (c_i, [c_fp] * 5 + [c_i] * 4 + [c_f, c_f, c_f, c_fp]),
     "dvf_smooth_loss_fwd": (c_i, [c_fp] * 3 + [c_i] * 3 + [c_f, c_i, c_fp]),
     "dvf_smooth_partials_floats": (c_i64, [c_i] * 3),
     "dvf_smooth_loss_bwd": (c_i, [c_fp] * 3 + [c_i] * 3 + [c_f, c_fp]),

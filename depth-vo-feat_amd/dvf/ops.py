@@ -308,6 +308,62 @@ class SmoothLossFn(torch.autograd.Function):
         return (None, *grads)
 
 
+class NormSmoothLossFn(torch.autograd.Function):
+    """Edge-aware first-order smoothness of the mean-normalised disparity over a list of scales (csrc/norm_smooth.hip;
+    build-side extension, monodepth2 form -- the reference has no such term, tests/normsmooth_ref.py is the definition):
+    sum_s w_s * loss(disp_s, img_s), w_{s+1} = w_s / scale_factor, w_0 = 1.
+
+    Inputs: cfg = (scale_factor, in_scale, eps), then the pairs disp_0, img_0, disp_1, img_1, ... with disp_s [B,1,H_s,W_s]
+    and img_s [B,C,H_s,W_s].  Only the disparities receive a gradient.  Output: 0-dim loss."""
+
+    @staticmethod
+    def forward(ctx, cfg, *pairs):
+        scale_factor, in_scale, eps = cfg
+        if not pairs or len(pairs) % 2:
+            raise ValueError("NormSmoothLossFn takes (disparity, image) pairs")
+        disps, imgs = [_f32c(d) for d in pairs[0::2]], [_f32c(i) for i in pairs[1::2]]
+        for d, i in zip(disps, imgs):
+            if d.dim() != 4 or i.dim() != 4 or d.shape[1] != 1 or (d.shape[0],) + tuple(d.shape[2:]) != (i.shape[0],) + tuple(i.shape[2:]):
+                raise ValueError(f"disparity {tuple(d.shape)} does not match image {tuple(i.shape)}")
+        lib = L.lib()
+        out = torch.empty(1, device=disps[0].device)
+        weights, stats, w = [], [], 1.0
+        for s, (d, i) in enumerate(zip(disps, imgs)):
+            B, C, H, W = i.shape
+            st = torch.empty(B, 2, device=d.device)
+            partials = torch.empty(int(lib.dvf_norm_smooth_partials_floats(B, H, W)), device=d.device)
+            with L.timed("normsmooth_fwd", 0.0, 4.0 * (1 + C) * B * H * W):
+                L.check(lib.dvf_norm_smooth_fwd(L.dev(d, "disparity"), L.dev(i, "img"), L.dev(out), L.dev(st), L.dev(partials),
+                                                B, C, H, W, in_scale, eps, w, 1 if s > 0 else 0, L.stream()),
+                        "dvf_norm_smooth_fwd")
+            weights.append(w)
+            stats.append(st)
+            w /= scale_factor
+        ctx.save_for_backward(*disps, *imgs, *stats)
+        ctx.cfg, ctx.weights = (in_scale, eps), weights
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gloss):
+        n = len(ctx.weights)
+        saved = ctx.saved_tensors
+        disps, imgs, stats = saved[:n], saved[n:2 * n], saved[2 * n:]
+        in_scale, eps = ctx.cfg
+        gl = _f32c(gloss).reshape(1)
+        grads = []
+        for s, (d, i, st, w) in enumerate(zip(disps, imgs, stats, ctx.weights)):
+            if not ctx.needs_input_grad[1 + 2 * s]:
+                grads += [None, None]
+                continue
+            B, C, H, W = i.shape
+            g = torch.empty_like(d)
+            with L.timed("normsmooth_bwd", 0.0, 4.0 * (2 + C) * B * H * W):
+                L.check(L.lib().dvf_norm_smooth_bwd(L.dev(d), L.dev(i), L.dev(st), L.dev(gl, "grad_loss"), L.dev(g), B, C, H, W,
+                                                    in_scale, eps, w, L.stream()), "dvf_norm_smooth_bwd")
+            grads += [g, None]
+        return (None, *grads)
+
+
 class EdgeSmoothLossFn(torch.autograd.Function):
     """Edge-aware first-order smoothness of the inverse depth as the reference's Caffe graph defines it
     (experiments/depth_odometry_feature/train.prototxt:4452-4661): see csrc/paper_losses.hip."""

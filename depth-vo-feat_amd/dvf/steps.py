@@ -57,11 +57,13 @@ def _identity_share(counts, n_views):
 
 def unsupervise_losses(depth_net, pose_net, batch, feat_extractor=None, img_scale=0.004, smooth_weight=10.0,
                        feat_weight=0.1, depth_eps=1e-4, ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4, min_reprojection=False,
-                       auto_mask=False):
+                       auto_mask=False, normalized_smoothness=False):
     """unsupervise.py:83-111.  ssim_weight > 0 (extension): the image term becomes a * DSSIM + (1 - a) * L1; the feature
     term stays L1.  min_reprojection / auto_mask (extension): the image term takes the per-pixel minimum over the two
     views, with the unwarped references competing under auto_mask; terms["automask"] is then the share of pixels won by
-    an identity candidate."""
+    an identity candidate.  normalized_smoothness (extension, monodepth2 form): terms["smooth"] is the edge-aware first-order
+    smoothness of the mean-normalised DISPARITY against img_scale * R2 (LF.normalized_smooth_loss) instead of the second-order
+    smoothness of depth, under the same smooth_weight (monodepth2 uses 1e-3).  Off: nothing changes."""
     counts = []
     R2, R1, L2 = batch["img_R2"], batch["img_R1"], batch["img_L2"]
     # unsupervise.py:92,95 (cat(R2, R1) done virtually) and :94 (intended: finest disparity)
@@ -73,7 +75,10 @@ def unsupervise_losses(depth_net, pose_net, batch, feat_extractor=None, img_scal
                                                   ssim_weight=ssim_weight, ssim_c1=ssim_c1, ssim_c2=ssim_c2,
                                                   min_reprojection=min_reprojection, auto_mask=auto_mask,
                                                   selection_counts=counts)
-    smooth = LF.smooth_loss(depth.unsqueeze(1))                    # :102
+    if normalized_smoothness:
+        smooth = LF.normalized_smooth_loss(inv_depth, R2, img_scale=img_scale)
+    else:
+        smooth = LF.smooth_loss(depth.unsqueeze(1))                # :102
     terms = {"img": img_loss.detach(), "smooth": smooth.detach()}
     if auto_mask:
         terms["automask"] = _identity_share(counts[0], 2)
@@ -106,7 +111,7 @@ def depth_only_losses(depth_net, batch, img_scale=0.004, smooth_weight=10.0, dep
 def train_sfm_losses(disp_net, pose_exp_net, batch, w1=1.0, w2=0.0, w3=0.1, smooth_factor=2.0,
                      rotation_mode="euler", padding_mode="zeros", feat_extractor=None, feat_weight=0.1,
                      ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4, min_reprojection=False, auto_mask=False,
-                     full_res_multiscale=False):
+                     full_res_multiscale=False, normalized_smoothness=False):
     """train.py:179-203.  ssim_weight > 0 (extension): the 4-scale photometric term becomes a * DSSIM + (1 - a) * L1.
     min_reprojection / auto_mask (extension): the image term takes the per-pixel minimum over the views (the unwarped
     references competing under auto_mask) and no explainability mask, so w2 must be 0; terms["automask"] is the share of
@@ -116,7 +121,11 @@ def train_sfm_losses(disp_net, pose_exp_net, batch, w1=1.0, w2=0.0, w3=0.1, smoo
     bilinearly to the input resolution, turned into depth there (one fused pass, LS.full_resolution) and the photometric term
     of every scale warps the full-resolution references against the full-resolution target; gradients reach the coarse
     disparities and masks.  Smoothness, the explainability regulariser, the stereo-pose MSE and the feature term stay on the
-    native-scale maps; terms["automask"] is still the finest scale's share.  Off: nothing changes."""
+    native-scale maps; terms["automask"] is still the finest scale's share.  Off: nothing changes.
+    normalized_smoothness (extension, monodepth2 form): terms["smooth"] is the edge-aware first-order smoothness of the
+    mean-normalised DISPARITIES of every scale at its native resolution, also under full_res_multiscale, against the target
+    image (LS.normalized_smooth_loss) instead of the second-order smoothness of the depths, under the same w3 and
+    smooth_factor (monodepth2 uses w3 = 1e-3).  Off: nothing changes."""
     if min_reprojection and w2 > 0:
         raise ValueError("min_reprojection leaves the explainability mask out of the photometric term: w2 must be 0")
     tgt = batch["img_R2"]
@@ -135,7 +144,10 @@ def train_sfm_losses(disp_net, pose_exp_net, batch, w1=1.0, w2=0.0, w3=0.1, smoo
                                             rotation_mode, padding_mode, ssim_weight=ssim_weight, ssim_c1=ssim_c1,
                                             ssim_c2=ssim_c2, min_reprojection=min_reprojection, auto_mask=auto_mask,
                                             selection_counts=counts)                               # :191
-    l3 = LS.smooth_loss(depth, smooth_factor)                      # :200
+    if normalized_smoothness:
+        l3 = LS.normalized_smooth_loss(disparities, tgt, smooth_factor)
+    else:
+        l3 = LS.smooth_loss(depth, smooth_factor)                  # :200
     l4 = torch.nn.functional.mse_loss(pose[:, 1], batch["T_R2L"])  # :201  (24 floats: left to torch)
     loss = w1 * l1 + w3 * l3 + l4
     terms = {"photo": l1.detach(), "smooth": l3.detach(), "lr": l4.detach()}
@@ -157,12 +169,14 @@ def train_sfm_losses(disp_net, pose_exp_net, batch, w1=1.0, w2=0.0, w3=0.1, smoo
     return loss, terms
 
 
-def unsupervise_dvo_losses(depth_net, pose_net, batch, img_scale=0.004, smooth_weight=10.0, depth_eps=1e-4):
+def unsupervise_dvo_losses(depth_net, pose_net, batch, img_scale=0.004, smooth_weight=10.0, depth_eps=1e-4,
+                           normalized_smoothness=False):
     """unsupervise_dvo.py:83-122 (the Caffe-style chain): T = (T_R2L, T_2to1) as se(3) vectors -> exponential map
     (t = R u) -> GeoTransform -> PinHole -> InverseWarping in PIXEL coordinates -> exact-zero-masked L1 for the
     stereo (L2 -> R2) and temporal (R1 -> R2) warps + 10 * smooth(depth).  All of it is the fused warp kernel with the
     DVF_POSE_SE3 | DVF_PIXEL_COORDS front end.  batch["T_R2L"] must be in the se(3) order (w, u), i.e. (0,0,0,Tx,0,0)
-    as the reference dataset writes it (data/dataset_builder.py:155)."""
+    as the reference dataset writes it (data/dataset_builder.py:155).  normalized_smoothness (extension): as in
+    unsupervise_losses."""
     from dvf.ops import PhotoLossFn
     R2, R1, L2 = batch["img_R2"], batch["img_R1"], batch["img_L2"]
     (_, T_2to1), disps = _side_by_side(lambda: pose_net((R2, R1)), lambda: depth_net(R2))
@@ -171,7 +185,7 @@ def unsupervise_dvo_losses(depth_net, pose_net, batch, img_scale=0.004, smooth_w
     pose = torch.stack((batch["T_R2L"], T_2to1), dim=0)                    # [V=2,B,6]: view 0 = left image, view 1 = R1
     photo = PhotoLossFn.apply(R2, depth.squeeze(1), pose, batch["K"], batch["Kinv"], None,
                               (L.POSE_SE3 | L.PIXEL_COORDS, float(img_scale)), L2, R1)
-    smooth = LF.smooth_loss(depth)
+    smooth = LF.normalized_smooth_loss(inv_depth, R2, img_scale=img_scale) if normalized_smoothness else LF.smooth_loss(depth)
     loss = photo + smooth_weight * smooth
     return loss, {"photo": photo.detach(), "smooth": smooth.detach(), "total": loss.detach()}
 

@@ -56,3 +56,12 @@ def smooth_loss(pred_map, scale_factor=1):
     if type(pred_map) not in [tuple, list]:
         pred_map = [pred_map]
     return SmoothLossFn.apply(float(scale_factor), *pred_map)
+
+
+def normalized_smooth_loss(disp, img, img_scale=1.0, eps=1e-7):
+    """Edge-aware first-order smoothness of the mean-normalised disparity, single scale (extension, monodepth2 form; the
+    reference has no such term: parity unpinned, tests/normsmooth_ref.py is the definition): with n = disp / (mean over the
+    image of disp + eps) and I = img_scale * img, mean(exp(-mean_c |dx I|) |dx n|) + mean(exp(-mean_c |dy I|) |dy n|).
+    disp [B,1,H,W], img [B,C,H,W]; only disp receives a gradient.  monodepth2 weighs the term with 1e-3."""
+    from dvf.ops import NormSmoothLossFn
+    return NormSmoothLossFn.apply((1.0, float(img_scale), float(eps)), disp, img)

@@ -109,6 +109,22 @@ def smooth_loss(pred_map, scale_factor):
     return SmoothLossFn.apply(float(scale_factor), *pred_map)
 
 
+def normalized_smooth_loss(disparities, tgt_img, scale_factor=2.0, img_scale=1.0, eps=1e-7):
+    """Edge-aware first-order smoothness of the mean-normalised DISPARITY, weight divided by ``scale_factor`` per scale
+    (extension, monodepth2 form; the reference has no such term: parity unpinned, tests/normsmooth_ref.py is the definition).
+    Per scale: n = disp / (mean over the image of disp + eps); mean(exp(-mean_c |dx I|) |dx n|) + mean(exp(-mean_c |dy I|) |dy n|)
+    with I = img_scale * tgt_img brought to the scale's size by ``area_downsample`` (a map at the image's own size takes the
+    image as it is).  Only the disparities receive a gradient.  dvf.ops.NormSmoothLossFn: one forward pass and one backward
+    launch per scale.  monodepth2 weighs the term with 1e-3."""
+    from dvf.ops import NormSmoothLossFn
+    if type(disparities) not in [tuple, list]:
+        disparities = [disparities]
+    pairs = []
+    for d in disparities:
+        pairs += [d, area_downsample(tgt_img, tuple(d.shape[2:]))]
+    return NormSmoothLossFn.apply((float(scale_factor), float(img_scale), float(eps)), *pairs)
+
+
 @torch.no_grad()
 def compute_errors(gt, pred, crop=True):
     """Evaluation-only depth metrics, same contract as the reference helper (loss_functions_sfm.py:80-116):

@@ -75,7 +75,8 @@ def main():
     def loss_fn(batch):
         return train_sfm_losses(disp_net, pose_exp_net, batch, args.photo_loss_weight, args.mask_loss_weight,
                                 args.smooth_loss_weight, args.smooth_loss_factor, args.rotation_mode, args.padding_mode,
-                                **cli.ssim_kwargs(args), **cli.minreproj_kwargs(args), **cli.fullres_kwargs(args))
+                                **cli.ssim_kwargs(args), **cli.minreproj_kwargs(args), **cli.fullres_kwargs(args),
+                                **cli.normsmooth_kwargs(args))
 
     terms = ["total", "photo", "smooth", "lr"] + (["exp"] if args.mask_loss_weight > 0 else []) + \
         (["automask"] if args.auto_mask else [])

@@ -37,6 +37,8 @@ parser.add_argument("-j", "--workers", default=4, type=int, metavar="N")
 parser.add_argument("--log-interval", type=int, default=10, metavar="N")
 parser.add_argument("--output-dir", type=str, default="./checkpoints")
 parser.add_argument("--features", action="store_true", help="add the 0.1 * feature-reconstruction term (FeatExtractor)")
+parser.add_argument("--smooth-weight", type=float, default=10.0, metavar="W",
+                    help="weight of the smoothness term (unsupervise.py:102,111 hard-code 10; with --normalized-smoothness use 0.001)")
 cli.add_common_flags(parser)
 
 
@@ -67,8 +69,8 @@ def main():
         n.to(args._device).train()
 
     def loss_fn(batch):
-        return unsupervise_losses(depth_net, odometry_net, batch, feat_extractor=feat, **cli.ssim_kwargs(args),
-                                  **cli.minreproj_kwargs(args))
+        return unsupervise_losses(depth_net, odometry_net, batch, feat_extractor=feat, smooth_weight=args.smooth_weight,
+                                  **cli.ssim_kwargs(args), **cli.minreproj_kwargs(args), **cli.normsmooth_kwargs(args))
 
     terms = ["total", "img", "smooth"] + (["feat"] if feat is not None else []) + (["automask"] if args.auto_mask else [])
     cli.run_training(args, nets, loss_fn, args.lr, (0.9, 0.999), args.weight_decay, terms, ckpts)

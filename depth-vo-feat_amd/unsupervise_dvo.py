@@ -35,6 +35,8 @@ parser.add_argument("--test-sequences", default=["00"], type=str, nargs="*")
 parser.add_argument("-j", "--workers", default=4, type=int, metavar="N")
 parser.add_argument("--log-interval", type=int, default=10, metavar="N")
 parser.add_argument("--output-dir", type=str, default="./checkpoints")
+parser.add_argument("--smooth-weight", type=float, default=10.0, metavar="W",
+                    help="weight of the smoothness term (unsupervise_dvo.py:122 hard-codes 10; with --normalized-smoothness use 0.001)")
 cli.add_common_flags(parser)
 
 
@@ -60,7 +62,8 @@ def main():
         # (data/dataset_builder.py:155); both the synthetic stream and un_dataset.to_batch provide it under this key
         b = dict(batch)
         b["T_R2L"] = batch["T_R2L_se3"]
-        return unsupervise_dvo_losses(depth_net, odometry_net, b)
+        return unsupervise_dvo_losses(depth_net, odometry_net, b, smooth_weight=args.smooth_weight,
+                                      **cli.normsmooth_kwargs(args))
 
     cli.run_training(args, [odometry_net, depth_net], loss_fn, args.lr, (0.9, 0.999), args.weight_decay,
                      ["total", "photo", "smooth"],

@@ -217,6 +217,31 @@ int dvf_minreproj_bwd(const float *tgt, const float *const *cands, int V, int au
                       const float *grad_loss, float *g_tgt, float *const *g_warped, int B, int C, int H, int W, float in_scale,
                       float alpha, float c1, float c2, void *stream);
 
+/* ---------------------------------------------------------------- edge-aware smoothness of the mean-normalised disparity
+ * (extension, opt-in).  The regulariser of the monodepth2 recipe; the reference's smoothness terms are the second-order one
+ * below and the Caffe graph's un-normalised one above, so there is NO reference call site, parity is unpinned and
+ * tests/normsmooth_ref.py is the definition.  disp [B,1,H,W], I = fl(in_scale * img) with img [B,C,H,W]; per image b:
+ *   m_b  = mean over (H,W) of disp_b                      n = disp / (m_b + eps)
+ *   wx   = exp(-mean_c |I(y,x) - I(y,x+1)|)               wy = exp(-mean_c |I(y,x) - I(y+1,x)|)
+ *   loss_out[0] (+)= weight * (mean(wx |n(y,x) - n(y,x+1)|) + mean(wy |n(y,x) - n(y+1,x)|))       (accumulate != 0 adds)
+ *   the two means over B*H*(W-1) and B*(H-1)*W elements; only disp receives a gradient; d|v|/dv = 0 at v = 0.
+ * With the mean fixed the term is linear in |delta disp|, so the forward is ONE tile pass over disp and img that leaves three
+ *   sums per block (sum disp, Sx = sum wx |dx disp|, Sy = sum wy |dy disp|) in `partials` (>= dvf_norm_smooth_partials_floats(B,H,W)
+ *   floats) plus one small finishing launch: stats [B,2] = (m_b + eps, T_b), T_b = Sx_b / (B H (W-1)) + Sy_b / (B (H-1) W),
+ *   loss = weight * sum_b T_b / |m_b + eps|.  Every sum is taken in a fixed order, without atomics: bit-reproducible.
+ * Backward (one launch, gather form, no atomics): stats is the forward's output, grad_loss a DEVICE scalar; every pixel collects
+ *   sign(delta) * w from its up to four neighbours (weights recomputed from the image) into A_p, which carries the two 1/count
+ *   factors, and writes g_disp [B,1,H,W] = grad_loss * weight * (A_p / (m_b + eps) - T_b / ((m_b + eps)^2 H W)) (for a negative
+ *   mean the first denominator is |m_b + eps| and the second keeps its sign).  Every element is written exactly once, nothing
+ *   needs zeroing.
+ * Checked on the host before anything is launched: DVF_ERR_INVALID_ARG for a null pointer, B <= 0, C <= 0, H < 2 or W < 2 (a mean
+ *   over W-1 or H-1 elements would be empty), B > 65535, C*H*W >= 2^31.  No allocation, no synchronisation: capturable. */
+int64_t dvf_norm_smooth_partials_floats(int B, int H, int W);
+int dvf_norm_smooth_fwd(const float *disp, const float *img, float *loss_out, float *stats, float *partials, int B, int C, int H,
+                        int W, float in_scale, float eps, float weight, int accumulate, void *stream);
+int dvf_norm_smooth_bwd(const float *disp, const float *img, const float *stats, const float *grad_loss, float *g_disp, int B,
+                        int C, int H, int W, float in_scale, float eps, float weight, void *stream);
+
 /* ---------------------------------------------------------------- smoothness loss
  * Replaces one map of smooth_loss (loss_functions.py:23-41 ; loss_functions_sfm.py:59-77):
  * weight * (mean|dx2| + mean|dxdy| + mean|dydx| + mean|dy2|) of a [N,H,W] stack of planes (N = B*C).
