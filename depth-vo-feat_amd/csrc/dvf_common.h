@@ -49,3 +49,37 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+
+// Fixed-order sum over a 256-thread block (four waves): wave_sum, one float per wave into red[4], then (r0 + r1) + (r2 + r3);
+// every thread returns the total.  `wave` is the caller's wave index (threadIdx.x >> 6 in a 1-D block, threadIdx.y in a
+// 64x4 one).  A caller that uses the same `red` again puts a __syncthreads() between the two calls.
+__device__ __forceinline__ float block_sum(float v, int wave, float *red) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[wave] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// Sum of partials[i * stride + offset], i < n, by a 1-D block of 256 threads: thread t adds i = t, t + 256, ... in that order,
+// then block_sum.
+__device__ __forceinline__ float block_sum_strided(const float *partials, int64_t n, int stride, int offset, float *red) {
+    float s = 0.f;
+    for (int64_t i = threadIdx.x; i < n; i += 256) s += partials[i * stride + offset];
+    return block_sum(s, threadIdx.x >> 6, red);
+}
+
+// Row-major index of this block in its grid: the slot of its record in a per-block partials array.
+__device__ __forceinline__ int64_t linear_block() {
+    return ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+}
+
+__device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
+
+// loss_out[0] (+)= scale * sum(partials[0 .. nblk)): the one-block second stage of the two-stage loss sums (elementwise.hip).
+int dvf_sum_partials(const float *partials, int64_t nblk, float scale, float *loss_out, int accumulate, hipStream_t st);
+
+// Image-shaped loss inputs: a grid with the B images in z, planes of at least min_side x min_side, 32-bit offsets within an
+// image.  (fill_photo_args of photo_loss.hip spells the same test out: it reports the last clause as DVF_ERR_UNSUPPORTED.)
+static inline bool image_shape_ok(int B, int C, int H, int W, int min_side) {
+    return B > 0 && C > 0 && H >= min_side && W >= min_side && B <= 65535 && (int64_t)C * H * W < ((int64_t)1 << 31);
+}

@@ -1,6 +1,7 @@
 // Memory-bound helpers of the training step: bilinear x2 upsampling (DispNetS disparity pyramid),
 // reciprocal (disparity -> depth), spatial mean (pose head), area down-sampling (sfm image pyramid),
-// bilinear x0.5 (FeatExtractor image pyramid) and the fused multi-tensor Adam update.
+// bilinear x0.5 (FeatExtractor image pyramid), the fused multi-tensor Adam update, the explainability BCE and the one-block
+// finish of the two-stage loss sums (dvf_sum_partials: BCE, SSIM + L1, Caffe edge-aware smoothness).
 #include "bilinear_src.h"
 #include "dvf_common.h"
 
@@ -143,24 +144,16 @@ __global__ __launch_bounds__(256) void bce_ones_fwd_kernel(const float *m, float
     float s = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
         s -= fmaxf(logf(m[i]), -100.f);
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    s = block_sum(s, threadIdx.x >> 6, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
-__global__ __launch_bounds__(256) void sum_partials_kernel(const float *partials, int nblk, float scale, float *out,
+// The second stage of every two-stage loss sum with one float per block: fixed order, so the loss is bit-reproducible.
+__global__ __launch_bounds__(256) void sum_partials_kernel(const float *partials, int64_t nblk, float scale, float *out,
                                                            int accumulate) {
     __shared__ float red[4];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < nblk; i += 256) s += partials[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float t = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
-        out[0] = accumulate ? out[0] + t : t;
-    }
+    const float t = block_sum_strided(partials, nblk, 1, 0, red) * scale;
+    if (threadIdx.x == 0) out[0] = accumulate ? out[0] + t : t;
 }
 
 // aten's binary_cross_entropy backward with target 1: g * (m - 1) / max((1 - m) * m, 1e-12).  Not the derivative of the
@@ -279,6 +272,12 @@ inline int nblocks(int64_t n) {
 
 }  // namespace
 
+int dvf_sum_partials(const float *partials, int64_t nblk, float scale, float *loss_out, int accumulate, hipStream_t st) {
+    sum_partials_kernel<<<1, 256, 0, st>>>(partials, nblk, scale, loss_out, accumulate);
+    DVF_LAUNCH_CHECK();
+    return DVF_OK;
+}
+
 extern "C" {
 
 int dvf_resize_bilinear_fwd(const float *in, float *out, int planes, int H, int W, int OH, int OW, float scale_h,
@@ -372,9 +371,7 @@ int dvf_bce_ones_fwd(const float *mask, float *loss_out, float *partials, int64_
     const int nb = nblocks(n) > 1024 ? 1024 : nblocks(n);
     bce_ones_fwd_kernel<<<nb, 256, 0, st>>>(mask, partials, n);
     DVF_LAUNCH_CHECK();
-    sum_partials_kernel<<<1, 256, 0, st>>>(partials, nb, 1.f / (float)n, loss_out, accumulate);
-    DVF_LAUNCH_CHECK();
-    return DVF_OK;
+    return dvf_sum_partials(partials, nb, 1.f / (float)n, loss_out, accumulate, st);
 }
 
 int dvf_bce_ones_bwd(const float *mask, const float *grad_loss, float *g_mask, int64_t n, void *stream) {

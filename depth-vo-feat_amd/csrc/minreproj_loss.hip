@@ -86,7 +86,7 @@ __global__ __launch_bounds__(NT) void minreproj_fwd_kernel(const float *tgt, Min
         select[(int64_t)n * plane + (int64_t)gy * W + gx] = (uint8_t)sel[r];
         if (sel[r] != NONE) s += best[r];
     }
-    s = wave_sum(s);
+    s = wave_sum(s);                                                    // block_sum written out: the counts share its barrier
     if (lx == 0) red[threadIdx.x >> 6] = s;
     for (int cat = 0; cat <= K; ++cat) {                                // cat == K counts "none"
         const int want = cat < K ? cat : NONE;
@@ -96,8 +96,7 @@ __global__ __launch_bounds__(NT) void minreproj_fwd_kernel(const float *tgt, Min
         if (lx == 0) redc[threadIdx.x >> 6][cat] = cnt;
     }
     __syncthreads();
-    const int64_t nblk = (int64_t)gridDim.x * gridDim.y * gridDim.z;
-    const int64_t blk = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    const int64_t nblk = (int64_t)gridDim.x * gridDim.y * gridDim.z, blk = linear_block();
     if (threadIdx.x == 0) partials[blk] = (red[0] + red[1]) + (red[2] + red[3]);
     if (threadIdx.x <= K)
         cnt_partials[threadIdx.x * nblk + blk] = redc[0][threadIdx.x] + redc[1][threadIdx.x] + redc[2][threadIdx.x] + redc[3][threadIdx.x];
@@ -107,15 +106,8 @@ __global__ __launch_bounds__(256) void minreproj_reduce_kernel(const float *part
                                                                float scale, float *loss_out, int *counts, int accumulate) {
     __shared__ float red[4];
     __shared__ int redc[4];
-    float s = 0.f;
-    for (int64_t i = threadIdx.x; i < nblk; i += 256) s += partials[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float t = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
-        loss_out[0] = accumulate ? loss_out[0] + t : t;
-    }
+    const float t = block_sum_strided(partials, nblk, 1, 0, red) * scale;
+    if (threadIdx.x == 0) loss_out[0] = accumulate ? loss_out[0] + t : t;
     for (int cat = 0; cat <= K; ++cat) {
         int c = 0;
         for (int64_t i = threadIdx.x; i < nblk; i += 256) c += cnt_partials[cat * nblk + i];
@@ -160,15 +152,7 @@ __global__ __launch_bounds__(NT) void minreproj_bwd_kernel(const float *tgt, Min
             for (int i = threadIdx.x; i < RH * RW; i += NT) {
                 float4 kf = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (ssel[i] == k) {                                 // in the image, and this candidate won the window
-                    const SsimWin w = ssim_window(sx, sy, (i / RW) * SW + i % RW + 2, c1, c2);
-                    constexpr float ninth = 1.f / 9.f;
-                    const float ib = 1.f / (w.b1 * w.b2);
-                    const float Q = 2.f * ninth * w.a1 * ib;
-                    const float R = -2.f * ninth * w.ssim / w.b2;
-                    const float Px = ninth * (2.f * w.my * w.a2 * ib - 2.f * w.mx * w.ssim / w.b1) - Q * w.my - R * w.mx;
-                    const float Py = ninth * (2.f * w.mx * w.a2 * ib - 2.f * w.my * w.ssim / w.b1) - Q * w.mx - R * w.my;
-                    const float f = -0.5f * alpha * w.gate * gl;                    // dssim = (1 - SSIM) / 2
-                    kf = make_float4(f * Px, f * Py, f * Q, f * R);
+                    kf = ring_coef(ssim_window(sx, sy, (i / RW) * SW + i % RW + 2, c1, c2), alpha, gl);
                 }
                 coef[i] = kf;
             }
@@ -177,6 +161,8 @@ __global__ __launch_bounds__(NT) void minreproj_bwd_kernel(const float *tgt, Min
             for (int r = 0; r < 4; ++r) {
                 const int ly = ly0 + r, gy = y0 + ly;
                 if (gx >= W || gy >= H) continue;
+                // ring_gather (ssim_window.h) written out: through the helper hipcc lays this kernel's address arithmetic out
+                // differently and it runs about 1 % slower.  Keep the two in step.
                 float ax = 0.f, ay = 0.f, q = 0.f, rr = 0.f;
 #pragma unroll
                 for (int dy = -1; dy <= 1; ++dy) {
@@ -192,9 +178,8 @@ __global__ __launch_bounds__(NT) void minreproj_bwd_kernel(const float *tgt, Min
                     }
                 }
                 const float xc = sx[(ly + 2) * SW + lx + 4], yc = sy[(ly + 2) * SW + lx + 4];
-                const float diff = yc - xc;
-                const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-                const float l1 = ssel[(ly + 1) * RW + lx + 1] == k ? (1.f - alpha) * gl * sgn : 0.f;
+                const float diff = yc - xc, sg = sgn(diff);
+                const float l1 = ssel[(ly + 1) * RW + lx + 1] == k ? (1.f - alpha) * gl * sg : 0.f;
                 if (G) G[((int64_t)n * C + c) * plane + (int64_t)gy * W + gx] = in_scale * (ay + q * xc + rr * yc + l1);
                 gt[r] += ax + q * yc + rr * xc - l1;
             }
@@ -238,7 +223,7 @@ int64_t dvf_minreproj_partials_floats(int B, int H, int W, int K) {
 int dvf_minreproj_fwd(const float *tgt, const float *const *cands, int V, int auto_mask, float *loss_out, uint8_t *select,
                       int32_t *counts, float *partials, int B, int C, int H, int W, float in_scale, float alpha, float c1, float c2,
                       int accumulate, void *stream) {
-    if (!tgt || !cands || !loss_out || !select || !counts || !partials || V < 1 || V > MAX_V || !ssim_shape_ok(B, C, H, W))
+    if (!tgt || !cands || !loss_out || !select || !counts || !partials || V < 1 || V > MAX_V || !image_shape_ok(B, C, H, W, 3))
         return DVF_ERR_INVALID_ARG;
     const int K = auto_mask ? 2 * V : V;
     MinReprojPtrs p = {};
@@ -259,7 +244,7 @@ int dvf_minreproj_fwd(const float *tgt, const float *const *cands, int V, int au
 int dvf_minreproj_bwd(const float *tgt, const float *const *cands, int V, int auto_mask, const uint8_t *select,
                       const float *grad_loss, float *g_tgt, float *const *g_warped, int B, int C, int H, int W, float in_scale,
                       float alpha, float c1, float c2, void *stream) {
-    if (!tgt || !cands || !select || !grad_loss || V < 1 || V > MAX_V || !ssim_shape_ok(B, C, H, W)) return DVF_ERR_INVALID_ARG;
+    if (!tgt || !cands || !select || !grad_loss || V < 1 || V > MAX_V || !image_shape_ok(B, C, H, W, 3)) return DVF_ERR_INVALID_ARG;
     const int K = auto_mask ? 2 * V : V;
     MinReprojPtrs p = {};
     int vec = 0;

@@ -31,10 +31,6 @@ constexpr int TW = 64, TH = 16, NT = 256, ROWS = TH / (NT / 64);   // 4 vertical
 
 static inline dim3 ns_grid(int B, int H, int W) { return dim3((W + TW - 1) / TW, (H + TH - 1) / TH, B); }
 
-static inline bool ns_shape_ok(int B, int C, int H, int W) {
-    return B > 0 && C > 0 && H >= 2 && W >= 2 && B <= 65535 && (int64_t)C * H * W < ((int64_t)1 << 31);
-}
-
 // exp(-mean_c |I_p - I_q|) of the pixel pair at plane offsets p and q of one image.  CT: the channel count when it is known at
 // compile time (1 and 3: the channel loop unrolls and its loads are issued together), 0 = read it from C.
 template <int CT>
@@ -46,8 +42,6 @@ __device__ __forceinline__ float edge_weight(const float *__restrict__ I, int64_
     for (int c = 0; c < nc; ++c) s += fabsf(__fmul_rn(in_scale, I[c * plane + p]) - __fmul_rn(in_scale, I[c * plane + q]));
     return __expf(-s * inv_c);
 }
-
-__device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
 template <int CT>
 __global__ __launch_bounds__(NT) void norm_smooth_fwd_kernel(const float *__restrict__ disp, const float *__restrict__ img,
@@ -80,7 +74,7 @@ __global__ __launch_bounds__(NT) void norm_smooth_fwd_kernel(const float *__rest
     }
     __syncthreads();
     if (threadIdx.x < 3) {
-        const int64_t blk = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        const int64_t blk = linear_block();
         const float *r = red[threadIdx.x];
         partials[blk * 3 + threadIdx.x] = (r[0] + r[1]) + (r[2] + r[3]);
     }
@@ -160,7 +154,7 @@ int64_t dvf_norm_smooth_partials_floats(int B, int H, int W) {
 
 int dvf_norm_smooth_fwd(const float *disp, const float *img, float *loss_out, float *stats, float *partials, int B, int C, int H,
                         int W, float in_scale, float eps, float weight, int accumulate, void *stream) {
-    if (!disp || !img || !loss_out || !stats || !partials || !ns_shape_ok(B, C, H, W)) return DVF_ERR_INVALID_ARG;
+    if (!disp || !img || !loss_out || !stats || !partials || !image_shape_ok(B, C, H, W, 2)) return DVF_ERR_INVALID_ARG;
     hipStream_t st = dvf_stream(stream);
     const dim3 grid = ns_grid(B, H, W);
     if (C == 3) norm_smooth_fwd_kernel<3><<<grid, NT, 0, st>>>(disp, img, partials, C, H, W, in_scale);
@@ -177,7 +171,7 @@ int dvf_norm_smooth_fwd(const float *disp, const float *img, float *loss_out, fl
 int dvf_norm_smooth_bwd(const float *disp, const float *img, const float *stats, const float *grad_loss, float *g_disp, int B,
                         int C, int H, int W, float in_scale, float eps, float weight, void *stream) {
     (void)eps;   // stats already holds m_b + eps; the parameter keeps the pair's signatures parallel
-    if (!disp || !img || !stats || !grad_loss || !g_disp || !ns_shape_ok(B, C, H, W)) return DVF_ERR_INVALID_ARG;
+    if (!disp || !img || !stats || !grad_loss || !g_disp || !image_shape_ok(B, C, H, W, 2)) return DVF_ERR_INVALID_ARG;
     const float cx = (float)(1.0 / ((double)B * H * (W - 1))), cy = (float)(1.0 / ((double)B * (H - 1) * W));
     const float inv_hw = (float)(1.0 / ((double)H * W));
     const dim3 grid = ns_grid(B, H, W);

@@ -50,27 +50,8 @@ __global__ __launch_bounds__(256) void edge_smooth_fwd_kernel(const float *inv_d
         const EdgeVals e = edge_vals(inv_depth + (int64_t)n * H * W, img + (int64_t)n * C * H * W, C, H, W, y, x, in_scale, k);
         s = fabsf(e.wv * e.dv) + fabsf(e.wh * e.dh);
     }
-    s = wave_sum(s);
-    if (threadIdx.x == 0) red[threadIdx.y] = s;
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0) {
-        const int64_t blk = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        partials[blk] = (red[0] + red[1]) + (red[2] + red[3]);
-    }
-}
-
-__global__ __launch_bounds__(256) void edge_smooth_reduce_kernel(const float *partials, int64_t nblk, float scale, float *loss_out,
-                                                                 int accumulate) {
-    __shared__ float red[4];
-    float s = 0.f;
-    for (int64_t i = threadIdx.x; i < nblk; i += 256) s += partials[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float t = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
-        loss_out[0] = accumulate ? loss_out[0] + t : t;
-    }
+    s = block_sum(s, threadIdx.y, red);
+    if (threadIdx.x == 0 && threadIdx.y == 0) partials[linear_block()] = s;
 }
 
 // Gather-form backward: pixel (p, q) of D collects the four outputs whose stencils touch it.
@@ -109,22 +90,18 @@ int64_t dvf_edge_smooth_partials_floats(int B, int H, int W) {
 
 int dvf_edge_smooth_fwd(const float *inv_depth, const float *img, float *loss_out, float *partials, int B, int C, int H, int W,
                         float in_scale, float edge_k, float weight, int accumulate, void *stream) {
-    if (!inv_depth || !img || !loss_out || !partials || B <= 0 || C <= 0 || H < 3 || W < 3 || B > 65535 ||
-        (int64_t)C * H * W >= ((int64_t)1 << 31))
+    if (!inv_depth || !img || !loss_out || !partials || !image_shape_ok(B, C, H, W, 3))
         return DVF_ERR_INVALID_ARG;
     hipStream_t st = dvf_stream(stream);
     const dim3 grid = edge_grid(B, H, W);
     edge_smooth_fwd_kernel<<<grid, dim3(EX, EY), 0, st>>>(inv_depth, img, partials, C, H, W, in_scale, edge_k);
     DVF_LAUNCH_CHECK();
-    edge_smooth_reduce_kernel<<<1, 256, 0, st>>>(partials, (int64_t)grid.x * grid.y * grid.z, weight / (float)B, loss_out, accumulate);
-    DVF_LAUNCH_CHECK();
-    return DVF_OK;
+    return dvf_sum_partials(partials, (int64_t)grid.x * grid.y * grid.z, weight / (float)B, loss_out, accumulate, st);
 }
 
 int dvf_edge_smooth_bwd(const float *inv_depth, const float *img, const float *grad_loss, float *g_inv_depth, int B, int C, int H,
                         int W, float in_scale, float edge_k, float weight, void *stream) {
-    if (!inv_depth || !img || !grad_loss || !g_inv_depth || B <= 0 || C <= 0 || H < 3 || W < 3 || B > 65535 ||
-        (int64_t)C * H * W >= ((int64_t)1 << 31))
+    if (!inv_depth || !img || !grad_loss || !g_inv_depth || !image_shape_ok(B, C, H, W, 3))
         return DVF_ERR_INVALID_ARG;
     edge_smooth_bwd_kernel<<<edge_grid(B, H, W), dim3(EX, EY), 0, dvf_stream(stream)>>>(inv_depth, img, grad_loss, g_inv_depth, C, H,
                                                                                       W, in_scale, edge_k, weight / (float)B);

@@ -269,7 +269,7 @@ __global__ __launch_bounds__(256) void photo_fwd_kernel(PhotoArgs a) {
     }
     __syncthreads();
     if (tid < a.V) {
-        const int64_t blk = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        const int64_t blk = linear_block();
         a.partials[blk * a.V + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
     }
 }
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256) void photo_bwd_kernel(PhotoArgs a) {
     const float cx = c0x * d, cy = c0y * d, cz = c0z * d;
     const float *tg = a.tgt + (int64_t)b * C * HW + pix;
     const bool need_tgt = a.g_tgt != nullptr;
-    const int64_t blk = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    const int64_t blk = linear_block();
     float gd = 0.f;
     float vmv[NV];                                          // validity * explainability * upstream / N per view
     uint32_t slo[NV], shi[NV];                              // L1 signs per (view, channel)

@@ -55,27 +55,8 @@ __global__ __launch_bounds__(NT) void ssim_fwd_kernel(const float *tgt, const fl
         if (gx < W && gy < H && nonzero[k])
             s += mask ? acc[k] * mask[(int64_t)n * mask_batch_stride + (int64_t)gy * W + gx] : acc[k];
     }
-    s = wave_sum(s);
-    if (lx == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int64_t blk = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        partials[blk] = (red[0] + red[1]) + (red[2] + red[3]);
-    }
-}
-
-__global__ __launch_bounds__(256) void ssim_reduce_kernel(const float *partials, int64_t nblk, float scale, float *loss_out,
-                                                          int accumulate) {
-    __shared__ float red[4];
-    float s = 0.f;
-    for (int64_t i = threadIdx.x; i < nblk; i += 256) s += partials[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float t = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
-        loss_out[0] = accumulate ? loss_out[0] + t : t;
-    }
+    s = block_sum(s, threadIdx.x >> 6, red);
+    if (threadIdx.x == 0) partials[linear_block()] = s;
 }
 
 __global__ __launch_bounds__(NT) void ssim_bwd_kernel(const float *tgt, const float *warped, const float *mask,
@@ -118,14 +99,7 @@ __global__ __launch_bounds__(NT) void ssim_bwd_kernel(const float *tgt, const fl
             float d = 0.f;
             if (y0 - 1 + ry >= 0 && y0 - 1 + ry < H && x0 - 1 + rx >= 0 && x0 - 1 + rx < W) {
                 const SsimWin w = ssim_window(sx, sy, ry * SW + rx + 2, c1, c2);
-                constexpr float ninth = 1.f / 9.f;
-                const float ib = 1.f / (w.b1 * w.b2);
-                const float Q = 2.f * ninth * w.a1 * ib;                        // d SSIM / d cxy * (1/9) ... per tap
-                const float R = -2.f * ninth * w.ssim / w.b2;
-                const float Px = ninth * (2.f * w.my * w.a2 * ib - 2.f * w.mx * w.ssim / w.b1) - Q * w.my - R * w.mx;
-                const float Py = ninth * (2.f * w.mx * w.a2 * ib - 2.f * w.my * w.ssim / w.b1) - Q * w.mx - R * w.my;
-                const float f = -0.5f * alpha * w.gate * wt;                    // dssim = (1 - SSIM) / 2
-                k = make_float4(f * Px, f * Py, f * Q, f * R);
+                k = ring_coef(w, alpha, wt);
                 d = alpha * w.dssim;
             }
             coef[i] = k;
@@ -136,27 +110,13 @@ __global__ __launch_bounds__(NT) void ssim_bwd_kernel(const float *tgt, const fl
         for (int r = 0; r < 4; ++r) {
             const int ly = ly0 + r, gy = y0 + ly;
             if (gx >= W || gy >= H) continue;
-            float ax = 0.f, ay = 0.f, q = 0.f, rr = 0.f;
-#pragma unroll
-            for (int dy = -1; dy <= 1; ++dy) {
-                const float wy = tap_count(gy, gy + dy, H);
-#pragma unroll
-                for (int dx = -1; dx <= 1; ++dx) {
-                    const float wgt = wy * tap_count(gx, gx + dx, W);
-                    const float4 k = coef[(ly + 1 + dy) * RW + lx + 1 + dx];
-                    ax += wgt * k.x;
-                    ay += wgt * k.y;
-                    q += wgt * k.z;
-                    rr += wgt * k.w;
-                }
-            }
+            const float4 s = ring_gather(coef, ly, lx, gy, gx, H, W);
             const float xc = sx[(ly + 2) * SW + lx + 4], yc = sy[(ly + 2) * SW + lx + 4];
             const float diff = yc - xc;
-            const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-            const float l1 = (1.f - alpha) * swt[(ly + 1) * RW + lx + 1] * sgn;
+            const float l1 = (1.f - alpha) * swt[(ly + 1) * RW + lx + 1] * sgn(diff);
             const int64_t o = ((int64_t)n * C + c) * plane + (int64_t)gy * W + gx;
-            if (g_warped) g_warped[o] = in_scale * (ay + q * xc + rr * yc + l1);
-            if (g_tgt) g_tgt[o] = in_scale * (ax + q * yc + rr * xc - l1);
+            if (g_warped) g_warped[o] = in_scale * (s.y + s.z * xc + s.w * yc + l1);
+            if (g_tgt) g_tgt[o] = in_scale * (s.x + s.z * yc + s.w * xc - l1);
             gm[r] += sd[(ly + 1) * RW + lx + 1] + (1.f - alpha) * fabsf(diff);
             nonzero[r] |= (yc != 0.f);
         }
@@ -184,7 +144,7 @@ int64_t dvf_ssim_partials_floats(int B, int H, int W) {
 int dvf_ssim_loss_fwd(const float *tgt, const float *warped, const float *mask, int64_t mask_batch_stride, float *loss_out,
                       float *partials, int B, int C, int H, int W, float in_scale, float alpha, float c1, float c2, int accumulate,
                       void *stream) {
-    if (!tgt || !warped || !loss_out || !partials || !ssim_shape_ok(B, C, H, W) || (mask && mask_batch_stride < (int64_t)H * W))
+    if (!tgt || !warped || !loss_out || !partials || !image_shape_ok(B, C, H, W, 3) || (mask && mask_batch_stride < (int64_t)H * W))
         return DVF_ERR_INVALID_ARG;
     hipStream_t st = dvf_stream(stream);
     const dim3 grid = ssim_grid(B, H, W);
@@ -192,15 +152,13 @@ int dvf_ssim_loss_fwd(const float *tgt, const float *warped, const float *mask, 
                                          ssim_vec(tgt, warped, W));
     DVF_LAUNCH_CHECK();
     const float scale = (float)(1.0 / ((double)B * C * H * W));
-    ssim_reduce_kernel<<<1, 256, 0, st>>>(partials, (int64_t)grid.x * grid.y * grid.z, scale, loss_out, accumulate);
-    DVF_LAUNCH_CHECK();
-    return DVF_OK;
+    return dvf_sum_partials(partials, (int64_t)grid.x * grid.y * grid.z, scale, loss_out, accumulate, st);
 }
 
 int dvf_ssim_loss_bwd(const float *tgt, const float *warped, const float *mask, int64_t mask_batch_stride, const float *grad_loss,
                       float *g_warped, float *g_tgt, float *g_mask, int B, int C, int H, int W, float in_scale, float alpha,
                       float c1, float c2, void *stream) {
-    if (!tgt || !warped || !grad_loss || !ssim_shape_ok(B, C, H, W) ||
+    if (!tgt || !warped || !grad_loss || !image_shape_ok(B, C, H, W, 3) ||
         ((mask || g_mask) && mask_batch_stride < (int64_t)H * W))
         return DVF_ERR_INVALID_ARG;
     if (!g_warped && !g_tgt && !g_mask) return DVF_OK;

@@ -1,5 +1,6 @@
 // Device and host helpers shared by the 3x3-window appearance kernels (ssim_loss.hip, minreproj_loss.hip): the 64x16 tile
-// geometry, plane staging with a reflected border, the window evaluation and the reflected-tap count of the gather backward.
+// geometry, plane staging with a reflected border, the window evaluation, and the gather backward: the ring windows' coefficients
+// (ring_coef) and their reflected-tap-counted sum per pixel (ring_gather).
 #pragma once
 #include "dvf_common.h"
 
@@ -91,11 +92,45 @@ __device__ __forceinline__ float tap_count(int p, int q, int n) {
     return ((q == 0 && p == 1) || (q == n - 1 && p == n - 2)) ? 2.f : 1.f;
 }
 
-inline dim3 ssim_grid(int B, int H, int W) { return dim3((W + TW - 1) / TW, (H + TH - 1) / TH, B); }
-
-inline bool ssim_shape_ok(int B, int C, int H, int W) {
-    return B > 0 && C > 0 && H >= 3 && W >= 3 && B <= 65535 && (int64_t)C * H * W < ((int64_t)1 << 31);
+// Gather backward, first half.  Within a window d dssim / d y_j = Py + Q x_j + R y_j is affine in the tap's own values (for
+// x: Px, with x and y swapped); returns (Px, Py, Q, R) times `weight` (and times alpha and the clamp gate of dssim).
+__device__ __forceinline__ float4 ring_coef(SsimWin w, float alpha, float weight) {
+    constexpr float ninth = 1.f / 9.f;
+    const float ib = 1.f / (w.b1 * w.b2);
+    const float Q = 2.f * ninth * w.a1 * ib;                        // d SSIM / d cxy * (1/9) ... per tap
+    const float R = -2.f * ninth * w.ssim / w.b2;
+    const float Px = ninth * (2.f * w.my * w.a2 * ib - 2.f * w.mx * w.ssim / w.b1) - Q * w.my - R * w.mx;
+    const float Py = ninth * (2.f * w.mx * w.a2 * ib - 2.f * w.my * w.ssim / w.b1) - Q * w.mx - R * w.my;
+    const float f = -0.5f * alpha * w.gate * weight;                // dssim = (1 - SSIM) / 2
+    float4 k;        // by value in, field by field out: make_float4 over a reference changes the contraction into FMAs
+    k.x = f * Px;
+    k.y = f * Py;
+    k.z = f * Q;
+    k.w = f * R;
+    return k;
 }
+
+// Second half: pixel (gy, gx), at (ly, lx) of the tile, sums the coefficients of the <= 9 ring windows that contain it; a
+// window that reaches the pixel through the reflected border counts twice per axis.
+__device__ __forceinline__ float4 ring_gather(const float4 *coef, int ly, int lx, int gy, int gx, int H, int W) {
+    float ax = 0.f, ay = 0.f, q = 0.f, r = 0.f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy) {
+        const float wy = tap_count(gy, gy + dy, H);
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const float wgt = wy * tap_count(gx, gx + dx, W);
+            const float4 k = coef[(ly + 1 + dy) * RW + lx + 1 + dx];
+            ax += wgt * k.x;
+            ay += wgt * k.y;
+            q += wgt * k.z;
+            r += wgt * k.w;
+        }
+    }
+    return make_float4(ax, ay, q, r);
+}
+
+inline dim3 ssim_grid(int B, int H, int W) { return dim3((W + TW - 1) / TW, (H + TH - 1) / TH, B); }
 
 inline int ssim_vec(const float *a, const float *b, int W) {
     return (W % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0) ? 1 : 0;

@@ -200,8 +200,6 @@ __device__ __forceinline__ void blend_grad(const Taps &t, const Samp &s, float &
     doy = -t.nw * ex - t.ne * dx + t.sw * ex + t.se * dx;
 }
 
-__device__ __forceinline__ float sgn(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }
-
 // Reduce 12 values per view over the block and add them to pose_ws[(v*B+b)*12 + k].
 // Wave stage = packed butterfly: at every step a lane hands HALF of its values to its partner and keeps the sum of
 // the other half, so 24 values cost 12+6+3 exchanges plus 3x3 plain steps (30 cross-lane ops instead of 24 x 6).

@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void smooth_fwd_kernel(const float *map, float
     __syncthreads();
     const int tid = threadIdx.y * SX + threadIdx.x;
     if (tid < 4) {
-        const int64_t blk = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        const int64_t blk = linear_block();
         partials[blk * 4 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
     }
 }
@@ -164,13 +164,8 @@ __global__ __launch_bounds__(256) void smooth_reduce_kernel(const float *partial
     const float wk[4] = {w0, w1, w2, w3};
     float total = 0.f;
     for (int k = 0; k < 4; ++k) {
-        float s = 0.f;
-        for (int64_t i = threadIdx.x; i < nblk; i += 256) s += partials[i * 4 + k];
-        s = wave_sum(s);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-        __syncthreads();
-        total += ((red[0] + red[1]) + (red[2] + red[3])) * wk[k];
-        __syncthreads();
+        total += block_sum_strided(partials, nblk, 4, k, red) * wk[k];
+        __syncthreads();                                   // red is written again for the next component
     }
     if (threadIdx.x == 0) loss_out[0] = accumulate ? loss_out[0] + total : total;
 }
