@@ -215,15 +215,13 @@ __global__ __launch_bounds__(256) void photo_fwd_kernel(PhotoArgs a) {
     const bool inside = x < W && y < H;
     const int pix = min(y, H - 1) * W + min(x, W - 1);
     const float d = a.depth[(int64_t)b * HW + pix];
-    // cam = (Kinv @ (u, v, 1)) * depth                      inverse_warp.py:38-40
-    const float u = (float)x, v = (float)y;
-    const float cx = (kinv[0] * u + kinv[1] * v + kinv[2]) * d;
-    const float cy = (kinv[3] * u + kinv[4] * v + kinv[5]) * d;
-    const float cz = (kinv[6] * u + kinv[7] * v + kinv[8]) * d;
+    float c0[3];
+    cam_ray(kinv, (float)x, (float)y, c0);
+    const float cam[3] = {c0[0] * d, c0[1] * d, c0[2] * d};
     const float *tg = a.tgt + (int64_t)b * C * HW + pix;
 #pragma unroll
     for (int vi = 0; vi < NV; ++vi) {
-        const Samp s = project<BORDER, ALIGN, PIX>(geo[vi], cx, cy, cz, W, H);
+        const Samp s = project<BORDER, ALIGN, PIX>(geo[vi], cam, W, H);
         const TapPos tp = tap_pos(s, W, H, inside);
         const Foot f = footprint(tp, a.vec, bbs, a.tile_floats, DVF_DBG(a, 16));
         float acc = 0.f;
@@ -327,7 +325,7 @@ template <bool BORDER, bool ALIGN, bool PIX, int NV>
 __global__ __launch_bounds__(256) void photo_bwd_kernel(PhotoArgs a) {
     __shared__ ViewGeo geo[DVF_MAX_VIEWS];
     __shared__ float kinv[9], kmat[9];
-    __shared__ float red[TY][DVF_MAX_VIEWS * 12];
+    __shared__ float red[TY][12];
     __shared__ int bbs[TY][4];
     extern __shared__ __attribute__((aligned(16))) float tile[];
     const int b = blockIdx.z, tid = threadIdx.y * TX + threadIdx.x;
@@ -339,11 +337,9 @@ __global__ __launch_bounds__(256) void photo_bwd_kernel(PhotoArgs a) {
     const int pix = min(y, H - 1) * W + min(x, W - 1);
     const float scale = a.caffe ? a.grad_loss[0] / (float)a.B : a.grad_loss[0] / ((float)a.B * (float)C * (float)H * (float)W);
     const float d = a.depth[(int64_t)b * HW + pix];
-    const float u = (float)x, v = (float)y;
-    const float c0x = kinv[0] * u + kinv[1] * v + kinv[2];
-    const float c0y = kinv[3] * u + kinv[4] * v + kinv[5];
-    const float c0z = kinv[6] * u + kinv[7] * v + kinv[8];
-    const float cx = c0x * d, cy = c0y * d, cz = c0z * d;
+    float c0[3];
+    cam_ray(kinv, (float)x, (float)y, c0);
+    const float cam[3] = {c0[0] * d, c0[1] * d, c0[2] * d};
     const float *tg = a.tgt + (int64_t)b * C * HW + pix;
     const bool need_tgt = a.g_tgt != nullptr;
     const int64_t blk = linear_block();
@@ -354,7 +350,7 @@ __global__ __launch_bounds__(256) void photo_bwd_kernel(PhotoArgs a) {
     // the L1 signs; then the chain to depth and to the [R|t] gradient partials of that view
 #pragma unroll
     for (int vi = 0; vi < NV; ++vi) {
-        const Samp s = project<BORDER, ALIGN, PIX>(geo[vi], cx, cy, cz, W, H);
+        const Samp s = project<BORDER, ALIGN, PIX>(geo[vi], cam, W, H);
         const TapPos tp = tap_pos(s, W, H, inside);
         const Foot f = footprint(tp, a.vec, bbs, a.tile_floats, DVF_DBG(a, 16));
         const float m = a.mask ? a.mask[((int64_t)b * NV + vi) * HW + pix] : 1.f;
@@ -410,24 +406,24 @@ __global__ __launch_bounds__(256) void photo_bwd_kernel(PhotoArgs a) {
         vmv[vi] = vm;
         if (a.g_mask && inside) a.g_mask[((int64_t)b * NV + vi) * HW + pix] = nz ? absum * sgn(m) * scale : 0.f;
         // chain to the projected point                       cam2pixel, inverse_warp.py:61-66
-        const float gxq = gix * vm * s.dix, gyq = giy * vm * s.diy;
-        const float gpx = gxq / s.Z, gpy = gyq / s.Z;
-        const float gpz = s.zpass ? -(gxq * s.xq + gyq * s.yq) / s.Z : 0.f;
+        float gp[3];
+        perspective_grad(gix * vm * s.dix, giy * vm * s.diy, s.xq, s.yq, s.Z, s.zpass, gp);
+        const float gpx = gp[0], gpy = gp[1], gpz = gp[2];
         const ViewGeo &g = geo[vi];
         // d p / d depth = (K R) cam0
         const float gcx = g.A[0] * gpx + g.A[3] * gpy + g.A[6] * gpz;
         const float gcy = g.A[1] * gpx + g.A[4] * gpy + g.A[7] * gpz;
         const float gcz = g.A[2] * gpx + g.A[5] * gpy + g.A[8] * gpz;
-        gd += nz ? gcx * c0x + gcy * c0y + gcz * c0z : 0.f;
+        gd += nz ? gcx * c0[0] + gcy * c0[1] + gcz * c0[2] : 0.f;
         if (a.pose_part) {
             // y = R cam + t ; g_y = K^T g_p ; g_t and g_R = g_y (x) cam ; reduced over the block and stored per block
             const float gyx = nz ? kmat[0] * gpx + kmat[3] * gpy + kmat[6] * gpz : 0.f;
             const float gyy = nz ? kmat[1] * gpx + kmat[4] * gpy + kmat[7] * gpz : 0.f;
             const float gyz = nz ? kmat[2] * gpx + kmat[5] * gpy + kmat[8] * gpz : 0.f;
-            float pacc[1][12] = {{gyx, gyy, gyz, gyx * cx, gyx * cy, gyx * cz, gyy * cx, gyy * cy, gyy * cz, gyz * cx, gyz * cy,
-                                  gyz * cz}};
+            const float pacc[12] = {gyx, gyy, gyz, gyx * cam[0], gyx * cam[1], gyx * cam[2], gyy * cam[0], gyy * cam[1],
+                                    gyy * cam[2], gyz * cam[0], gyz * cam[1], gyz * cam[2]};
             __syncthreads();                                // (red of the previous view fully read)
-            reduce_pose_partials<1>(pacc, 1, a.B, b, nullptr, red, a.pose_part + (blk * NV + vi) * 12);
+            reduce_pose_partials(pacc, red, a.pose_part + (blk * NV + vi) * 12, nullptr);
         }
     }
     if (a.g_depth && inside) a.g_depth[(int64_t)b * HW + pix] = gd;
@@ -459,7 +455,7 @@ __global__ __launch_bounds__(256) void photo_bwd_kernel(PhotoArgs a) {
     for (int vi = 0; vi < NV; ++vi) {
         float *gs = a.g_src[vi];
         if (!gs) continue;                                  // (block-uniform)
-        const Samp s = project<BORDER, ALIGN, PIX>(geo[vi], cx, cy, cz, W, H);
+        const Samp s = project<BORDER, ALIGN, PIX>(geo[vi], cam, W, H);
         const TapPos p = tap_pos(s, W, H, inside);
         const Foot f = footprint(p, a.vec, bbs, a.tile_floats, DVF_DBG(a, 16));
         // fixed-point scale from the block's largest |upstream value| (wave max -> LDS -> block max)
@@ -486,12 +482,7 @@ __global__ __launch_bounds__(256) void photo_bwd_kernel(PhotoArgs a) {
                 float *gp = gs + (int64_t)b * C * HW + s.y0 * W + s.x0;
                 for (int c = 0; c < C; ++c) {
                     const float g = sign_get(slo[vi], shi[vi], c) * gsc;
-                    if (g != 0.f) {
-                        if (p.v_nw) atomicAdd(gp, g * s.wnw);
-                        if (p.v_ne) atomicAdd(gp + 1, g * s.wne);
-                        if (p.v_sw) atomicAdd(gp + W, g * s.wsw);
-                        if (p.v_se) atomicAdd(gp + W + 1, g * s.wse);
-                    }
+                    if (g != 0.f) scatter4(gp, W, p, s, g);
                     gp += HW;
                 }
             }
@@ -537,7 +528,6 @@ __global__ __launch_bounds__(256) void photo_bwd_kernel(PhotoArgs a) {
     }
 }
 
-inline dim3 photo_grid(int B, int H, int W) { return dim3((W + TX - 1) / TX, (H + TY - 1) / TY, B); }
 inline int photo_tile_floats(int C) { const int t = (C < PT_CC ? C : PT_CC) * PT_CAP; return t < PT_MIN_TILE ? PT_MIN_TILE : t; }
 
 int fill_photo_args(PhotoArgs &a, const float *tgt, const float *const *srcs, int V, const float *depth,
@@ -564,17 +554,36 @@ int fill_photo_args(PhotoArgs &a, const float *tgt, const float *const *srcs, in
     return DVF_OK;
 }
 
+// Launch the forward or the backward kernel of the flags' sampling mode and of V views on its grid and LDS tile.
+int launch_photo(PhotoArgs &a, uint32_t flags, bool bwd, hipStream_t st) {
+    const int V = a.V;
+    a.tile_floats = photo_tile_floats(a.C);
+    return dispatch_mode(flags, [&](auto border, auto align, auto pix) {
+        constexpr bool BD = decltype(border)::value, AL = decltype(align)::value, PX = decltype(pix)::value;
+        void (*kernel)(PhotoArgs);
+        switch (V) {
+            case 1: kernel = bwd ? photo_bwd_kernel<BD, AL, PX, 1> : photo_fwd_kernel<BD, AL, PX, 1>; break;
+            case 2: kernel = bwd ? photo_bwd_kernel<BD, AL, PX, 2> : photo_fwd_kernel<BD, AL, PX, 2>; break;
+            case 3: kernel = bwd ? photo_bwd_kernel<BD, AL, PX, 3> : photo_fwd_kernel<BD, AL, PX, 3>; break;
+            default: kernel = bwd ? photo_bwd_kernel<BD, AL, PX, 4> : photo_fwd_kernel<BD, AL, PX, 4>; break;
+        }
+        kernel<<<pix_grid(a.B, a.H, a.W), dim3(TX, TY), (size_t)a.tile_floats * sizeof(float), st>>>(a);
+        DVF_LAUNCH_CHECK();
+        return DVF_OK;
+    });
+}
+
 }  // namespace
 
 extern "C" {
 
 int64_t dvf_photo_partials_floats(int B, int H, int W, int V) {
-    const dim3 g = photo_grid(B, H, W);
+    const dim3 g = pix_grid(B, H, W);
     return (int64_t)g.x * g.y * g.z * V;
 }
 
 int64_t dvf_photo_pose_ws_floats(int B, int H, int W, int V) {
-    const dim3 g = photo_grid(B, H, W);
+    const dim3 g = pix_grid(B, H, W);
     return (int64_t)g.x * g.y * g.z * V * 12 + (int64_t)V * B * 12;
 }
 
@@ -587,21 +596,9 @@ int dvf_photo_loss_fwd(const float *tgt, const float *const *srcs, int V, const 
     if (!loss_out || !partials) return DVF_ERR_INVALID_ARG;
     a.partials = partials;
     hipStream_t st = dvf_stream(stream);
-    const dim3 grid = photo_grid(B, H, W);
-    a.tile_floats = photo_tile_floats(C);
-    const size_t lds = (size_t)a.tile_floats * sizeof(float);
-    rc = dispatch_mode(flags, [&](auto border, auto align, auto pix) {
-        constexpr bool BD = decltype(border)::value, AL = decltype(align)::value, PX = decltype(pix)::value;
-        switch (V) {
-            case 1: photo_fwd_kernel<BD, AL, PX, 1><<<grid, dim3(TX, TY), lds, st>>>(a); break;
-            case 2: photo_fwd_kernel<BD, AL, PX, 2><<<grid, dim3(TX, TY), lds, st>>>(a); break;
-            case 3: photo_fwd_kernel<BD, AL, PX, 3><<<grid, dim3(TX, TY), lds, st>>>(a); break;
-            default: photo_fwd_kernel<BD, AL, PX, 4><<<grid, dim3(TX, TY), lds, st>>>(a); break;
-        }
-        DVF_LAUNCH_CHECK();
-        return DVF_OK;
-    });
+    rc = launch_photo(a, flags, false, st);
     if (rc != DVF_OK) return rc;
+    const dim3 grid = pix_grid(B, H, W);
     const float inv_n = (flags & DVF_CAFFE_ABSLOSS) ? 1.f / (float)B : 1.f / ((float)B * (float)C * (float)H * (float)W);
     photo_reduce_kernel<<<1, 1024, 0, st>>>(partials, (int64_t)grid.x * grid.y * grid.z, V, inv_n, loss_out, view_loss);
     DVF_LAUNCH_CHECK();
@@ -624,25 +621,11 @@ int dvf_photo_loss_bwd(const float *tgt, const float *const *srcs, int V, const 
     if ((g_tgt || any_src) && C > PT_MAXC) return DVF_ERR_UNSUPPORTED;      // (per-channel signs are kept in 64 bits)
     a.grad_loss = grad_loss;
     a.g_depth = g_depth; a.g_tgt = g_tgt; a.g_mask = g_mask;
-    const dim3 grid = photo_grid(B, H, W);
-    const int64_t nblk = (int64_t)grid.x * grid.y * grid.z;
     a.pose_part = g_pose ? pose_ws + (int64_t)V * B * 12 : nullptr;
     hipStream_t st = dvf_stream(stream);
-    a.tile_floats = photo_tile_floats(C);
-    const size_t lds = (size_t)a.tile_floats * sizeof(float);
-    rc = dispatch_mode(flags, [&](auto border, auto align, auto pix) {
-        constexpr bool BD = decltype(border)::value, AL = decltype(align)::value, PX = decltype(pix)::value;
-        switch (V) {
-            case 1: photo_bwd_kernel<BD, AL, PX, 1><<<grid, dim3(TX, TY), lds, st>>>(a); break;
-            case 2: photo_bwd_kernel<BD, AL, PX, 2><<<grid, dim3(TX, TY), lds, st>>>(a); break;
-            case 3: photo_bwd_kernel<BD, AL, PX, 3><<<grid, dim3(TX, TY), lds, st>>>(a); break;
-            default: photo_bwd_kernel<BD, AL, PX, 4><<<grid, dim3(TX, TY), lds, st>>>(a); break;
-        }
-        DVF_LAUNCH_CHECK();
-        return DVF_OK;
-    });
+    rc = launch_photo(a, flags, true, st);
     if (rc != DVF_OK) return rc;
-    (void)nblk;
+    const dim3 grid = pix_grid(B, H, W);
     if (g_pose) {
         pose_sum_kernel<<<V * B, 1024, 0, st>>>(a.pose_part, pose_ws, V, B, (int)(grid.x * grid.y));
         DVF_LAUNCH_CHECK();

@@ -1,5 +1,7 @@
-// Device helpers shared by the warp / photometric-loss translation units: pose -> rotation, the pixel -> cam -> SE3 ->
-// pixel chain of one (pixel, view), 2x2 tap addressing, bilinear blend and its gradient, the pose-gradient finalisation.
+// Device helpers shared by the warp / photometric-loss translation units: pose -> rotation, the camera ray and the pixel ->
+// cam -> SE3 -> pixel chain of one (pixel, view), 2x2 tap addressing, bilinear blend and its gradient, the perspective
+// division's backward, the guarded four-tap scatter, the reduction of one view's 12 [t|R] partials over a block and the
+// pose-gradient finalisation.
 // Arithmetic follows the reference op by op (file:line in each helper) in fp32; products/sums whose rounding decides an
 // exact comparison in the reference are written with __f*_rn so hipcc does not contract them into FMAs.
 #pragma once
@@ -77,6 +79,12 @@ static __device__ void build_view(const float *pose6, const float *K, int mode, 
     for (int i = 0; i < 3; ++i) g->tr[i] = K[i * 3 + 0] * t[0] + K[i * 3 + 1] * t[1] + K[i * 3 + 2] * t[2];
 }
 
+// c0 = Kinv @ (u, v, 1); the camera point is c0 * depth       inverse_warp.py:38-40
+__device__ __forceinline__ void cam_ray(const float *kinv, float u, float v, float (&c0)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) c0[i] = kinv[i * 3 + 0] * u + kinv[i * 3 + 1] * v + kinv[i * 3 + 2];
+}
+
 // Everything the sampler needs for one (pixel, view).
 struct Samp {
     float ix, iy;            // un-normalised source coordinates
@@ -88,8 +96,9 @@ struct Samp {
 };
 
 template <bool BORDER, bool ALIGN, bool PIX = false>
-__device__ __forceinline__ Samp project(const ViewGeo &g, float cx, float cy, float cz, int W, int H) {
+__device__ __forceinline__ Samp project(const ViewGeo &g, const float (&cam)[3], int W, int H) {
     Samp s;
+    const float cx = cam[0], cy = cam[1], cz = cam[2];
     // p = (K R) cam + K t                                   inverse_warp.py:55-60
     const float px = g.A[0] * cx + g.A[1] * cy + g.A[2] * cz + g.tr[0];
     const float py = g.A[3] * cx + g.A[4] * cy + g.A[5] * cz + g.tr[1];
@@ -200,74 +209,68 @@ __device__ __forceinline__ void blend_grad(const Taps &t, const Samp &s, float &
     doy = -t.nw * ex - t.ne * dx + t.sw * ex + t.se * dx;
 }
 
-// Reduce 12 values per view over the block and add them to pose_ws[(v*B+b)*12 + k].
-// Wave stage = packed butterfly: at every step a lane hands HALF of its values to its partner and keeps the sum of
-// the other half, so 24 values cost 12+6+3 exchanges plus 3x3 plain steps (30 cross-lane ops instead of 24 x 6).
-// `part` != nullptr: the block's sums are STORED to part[0 .. V*12) (deterministic two-stage reduction) instead.
-template <int NV>
-__device__ __forceinline__ void reduce_pose_partials(float (&acc)[NV][12], int V, int B, int b, float *pose_ws,
-                                                     float (*red)[DVF_MAX_VIEWS * 12], float *part = nullptr) {
-    constexpr int N = NV * 12;
-    float v[N];
-#pragma unroll
-    for (int vi = 0; vi < NV; ++vi)
-#pragma unroll
-        for (int k = 0; k < 12; ++k) v[vi * 12 + k] = acc[vi][k];
-    const int lane = threadIdx.x;                          // blockDim.x == 64: one wave per threadIdx.y
-    // halving steps on lane bits 5, 4, 3 (as long as the count stays even)
-    int base = 0;                                          // original index of v[0] in this lane
-    constexpr int N1 = N / 2, N2 = (N % 4 == 0) ? N / 4 : N1, N3 = (N % 8 == 0) ? N / 8 : N2;
+// Backward of xq = X / Z, yq = Y / Z with Z = max(pz, 1e-3): (d loss / d xq, d loss / d yq) -> gp = d loss / d (px, py, pz)
+// cam2pixel, inverse_warp.py:61-66
+__device__ __forceinline__ void perspective_grad(float gxq, float gyq, float xq, float yq, float Z, bool zpass, float (&gp)[3]) {
+    gp[0] = gxq / Z;
+    gp[1] = gyq / Z;
+    gp[2] = zpass ? -(gxq * xq + gyq * yq) / Z : 0.f;
+}
+
+// Scatter g * (the four bilinear weights) to the taps that `t` (a TapAddr or a TapPos) declares valid; gp points at
+// (y0, x0) of the destination plane.
+template <typename T>
+__device__ __forceinline__ void scatter4(float *gp, int W, const T &t, const Samp &s, float g) {
+    if (t.v_nw) atomicAdd(gp, g * s.wnw);
+    if (t.v_ne) atomicAdd(gp + 1, g * s.wne);
+    if (t.v_sw) atomicAdd(gp + W, g * s.wsw);
+    if (t.v_se) atomicAdd(gp + W + 1, g * s.wse);
+}
+
+// Reduce the 12 [t|R] partials of one view over the block (64 x 4 threads, one wave per threadIdx.y).
+// Wave stage = packed butterfly: at the first two steps a lane hands HALF of its values to its partner and keeps the sum
+// of the other half (6, then 3 exchanges), then 3 values take four plain steps: 21 cross-lane ops instead of 12 x 6.
+// `part` != nullptr: the block's sums are STORED to part[0 .. 12) (deterministic two-stage reduction); else they are added
+// to sum[0 .. 12) with float atomics.
+__device__ __forceinline__ void reduce_pose_partials(const float (&acc)[12], float (*red)[12], float *part, float *sum) {
+    const int lane = threadIdx.x;
+    float v[6];
+    int base = 0;                                          // index in acc of this lane's v[0]
     {
         const bool up = lane & 32;
 #pragma unroll
-        for (int i = 0; i < N1; ++i) {
-            const float send = up ? v[i] : v[i + N1], keep = up ? v[i + N1] : v[i];
+        for (int i = 0; i < 6; ++i) {
+            const float send = up ? acc[i] : acc[i + 6], keep = up ? acc[i + 6] : acc[i];
             v[i] = keep + __shfl_xor(send, 32, 64);
         }
-        base += up ? N1 : 0;
+        base += up ? 6 : 0;
     }
-    if (N2 != N1) {
+    {
         const bool up = lane & 16;
 #pragma unroll
-        for (int i = 0; i < N2; ++i) {
-            const float send = up ? v[i] : v[i + N2], keep = up ? v[i + N2] : v[i];
+        for (int i = 0; i < 3; ++i) {
+            const float send = up ? v[i] : v[i + 3], keep = up ? v[i + 3] : v[i];
             v[i] = keep + __shfl_xor(send, 16, 64);
         }
-        base += up ? N2 : 0;
-    } else {
-#pragma unroll
-        for (int i = 0; i < N1; ++i) v[i] += __shfl_xor(v[i], 16, 64);
-    }
-    if (N3 != N2) {
-        const bool up = lane & 8;
-#pragma unroll
-        for (int i = 0; i < N3; ++i) {
-            const float send = up ? v[i] : v[i + N3], keep = up ? v[i + N3] : v[i];
-            v[i] = keep + __shfl_xor(send, 8, 64);
-        }
-        base += up ? N3 : 0;
-    } else {
-#pragma unroll
-        for (int i = 0; i < N2; ++i) v[i] += __shfl_xor(v[i], 8, 64);
+        base += up ? 3 : 0;
     }
 #pragma unroll
-    for (int i = 0; i < N3; ++i) {
+    for (int i = 0; i < 3; ++i) {
         float t = v[i];
-        t += __shfl_xor(t, 4, 64);
-        t += __shfl_xor(t, 2, 64);
-        t += __shfl_xor(t, 1, 64);
+#pragma unroll
+        for (int off = 8; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
         v[i] = t;
     }
     if ((lane & 7) == 0) {
 #pragma unroll
-        for (int i = 0; i < N3; ++i) red[threadIdx.y][base + i] = v[i];
+        for (int i = 0; i < 3; ++i) red[threadIdx.y][base + i] = v[i];
     }
     __syncthreads();
     const int tid = threadIdx.y * TX + threadIdx.x;
-    if (tid < V * 12) {
+    if (tid < 12) {
         const float r = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
         if (part) part[tid] = r;
-        else atomicAdd(&pose_ws[((int64_t)(tid / 12) * B + b) * 12 + (tid % 12)], r);
+        else atomicAdd(&sum[tid], r);
     }
 }
 
@@ -398,6 +401,12 @@ inline int dispatch_mode(uint32_t flags, F &&f) {
     if (align) return f(N{}, T{}, N{});
     return f(N{}, N{}, N{});
 }
+
+// One block per TX x TY pixel tile, the B images in z.
+inline dim3 pix_grid(int B, int H, int W) { return dim3((W + TX - 1) / TX, (H + TY - 1) / TY, B); }
+
+// Blocks of 256 threads for a grid-stride loop over `total` elements.
+inline int grid_stride_blocks(int64_t total) { return (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256); }
 
 inline uint32_t rot_mode(uint32_t flags) { return (flags & DVF_POSE_SE3) ? 2u : ((flags & DVF_ROT_QUAT) ? 1u : 0u); }
 

@@ -31,7 +31,7 @@ template <bool BORDER, bool ALIGN, bool PIX, bool BWD>
 __global__ __launch_bounds__(256) void warp_kernel(WarpArgs a) {
     __shared__ ViewGeo geo;
     __shared__ float kinv[9], kmat[9];
-    __shared__ float red[TY][DVF_MAX_VIEWS * 12];
+    __shared__ float red[TY][12];
     const int b = blockIdx.z, tid = threadIdx.y * TX + threadIdx.x;
     if (tid == 0) build_view(a.pose + (int64_t)b * 6, a.K + (int64_t)b * 9, (int)a.quat, &geo);
     if (tid >= 64 && tid < 73) kinv[tid - 64] = a.Kinv[(int64_t)b * 9 + tid - 64];
@@ -40,18 +40,16 @@ __global__ __launch_bounds__(256) void warp_kernel(WarpArgs a) {
     const int x = blockIdx.x * TX + threadIdx.x, y = blockIdx.y * TY + threadIdx.y;
     const int W = a.W, H = a.H, C = a.C;
     const int64_t HW = (int64_t)H * W;
-    float pacc[1][12];
+    float pacc[12];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) pacc[0][k] = 0.f;
+    for (int k = 0; k < 12; ++k) pacc[k] = 0.f;
     if (x < W && y < H) {
         const int64_t pix = (int64_t)y * W + x;
         const float d = a.depth[(int64_t)b * HW + pix];
-        const float u = (float)x, v = (float)y;
-        const float c0x = kinv[0] * u + kinv[1] * v + kinv[2];
-        const float c0y = kinv[3] * u + kinv[4] * v + kinv[5];
-        const float c0z = kinv[6] * u + kinv[7] * v + kinv[8];
-        const float cx = c0x * d, cy = c0y * d, cz = c0z * d;
-        const Samp s = project<BORDER, ALIGN, PIX>(geo, cx, cy, cz, W, H);
+        float c0[3];
+        cam_ray(kinv, (float)x, (float)y, c0);
+        const float cam[3] = {c0[0] * d, c0[1] * d, c0[2] * d};
+        const Samp s = project<BORDER, ALIGN, PIX>(geo, cam, W, H);
         const float *sp = a.img + (int64_t)b * C * HW;
         if (!BWD) {
             float *op = a.out + (int64_t)b * C * HW + pix;
@@ -60,8 +58,6 @@ __global__ __launch_bounds__(256) void warp_kernel(WarpArgs a) {
         } else {
             const float *go = a.grad_out + (int64_t)b * C * HW + pix;
             float gix = 0.f, giy = 0.f;
-            const bool xin0 = (unsigned)s.x0 < (unsigned)W, xin1 = (unsigned)(s.x0 + 1) < (unsigned)W;
-            const bool yin0 = (unsigned)s.y0 < (unsigned)H, yin1 = (unsigned)(s.y0 + 1) < (unsigned)H;
             const TapAddr ta = tap_addr(s, W, H);
             for (int c = 0; c < C; ++c) {
                 const Taps t = gather(sp + c * HW, ta);
@@ -70,33 +66,27 @@ __global__ __launch_bounds__(256) void warp_kernel(WarpArgs a) {
                 blend_grad(t, s, dox, doy);
                 gix += g * dox;
                 giy += g * doy;
-                if (a.g_img) {
-                    float *gp = a.g_img + ((int64_t)b * C + c) * HW + (int64_t)s.y0 * W + s.x0;
-                    if (xin0 && yin0) atomicAdd(gp, g * s.wnw);
-                    if (xin1 && yin0) atomicAdd(gp + 1, g * s.wne);
-                    if (xin0 && yin1) atomicAdd(gp + W, g * s.wsw);
-                    if (xin1 && yin1) atomicAdd(gp + W + 1, g * s.wse);
-                }
+                if (a.g_img) scatter4(a.g_img + ((int64_t)b * C + c) * HW + (int64_t)s.y0 * W + s.x0, W, ta, s, g);
             }
-            const float gxq = gix * s.dix, gyq = giy * s.diy;
-            const float gpx = gxq / s.Z, gpy = gyq / s.Z;
-            const float gpz = s.zpass ? -(gxq * s.xq + gyq * s.yq) / s.Z : 0.f;
+            float gp[3];
+            perspective_grad(gix * s.dix, giy * s.diy, s.xq, s.yq, s.Z, s.zpass, gp);
+            const float gpx = gp[0], gpy = gp[1], gpz = gp[2];
             const float gcx = geo.A[0] * gpx + geo.A[3] * gpy + geo.A[6] * gpz;
             const float gcy = geo.A[1] * gpx + geo.A[4] * gpy + geo.A[7] * gpz;
             const float gcz = geo.A[2] * gpx + geo.A[5] * gpy + geo.A[8] * gpz;
-            if (a.g_depth) a.g_depth[(int64_t)b * HW + pix] = gcx * c0x + gcy * c0y + gcz * c0z;
+            if (a.g_depth) a.g_depth[(int64_t)b * HW + pix] = gcx * c0[0] + gcy * c0[1] + gcz * c0[2];
             const float gyx = kmat[0] * gpx + kmat[3] * gpy + kmat[6] * gpz;
             const float gyy = kmat[1] * gpx + kmat[4] * gpy + kmat[7] * gpz;
             const float gyz = kmat[2] * gpx + kmat[5] * gpy + kmat[8] * gpz;
-            pacc[0][0] = gyx; pacc[0][1] = gyy; pacc[0][2] = gyz;
-            pacc[0][3] = gyx * cx; pacc[0][4] = gyx * cy; pacc[0][5] = gyx * cz;
-            pacc[0][6] = gyy * cx; pacc[0][7] = gyy * cy; pacc[0][8] = gyy * cz;
-            pacc[0][9] = gyz * cx; pacc[0][10] = gyz * cy; pacc[0][11] = gyz * cz;
+            pacc[0] = gyx; pacc[1] = gyy; pacc[2] = gyz;
+            pacc[3] = gyx * cam[0]; pacc[4] = gyx * cam[1]; pacc[5] = gyx * cam[2];
+            pacc[6] = gyy * cam[0]; pacc[7] = gyy * cam[1]; pacc[8] = gyy * cam[2];
+            pacc[9] = gyz * cam[0]; pacc[10] = gyz * cam[1]; pacc[11] = gyz * cam[2];
         }
     }
     if (BWD && a.pose_ws) {
         float *part = a.pose_part ? a.pose_part + (((int64_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 12 : nullptr;
-        reduce_pose_partials<1>(pacc, 1, a.B, b, a.pose_ws, red, part);
+        reduce_pose_partials(pacc, red, part, a.pose_ws + (int64_t)b * 12);
     }
 }
 
@@ -235,15 +225,15 @@ __global__ void pixel2cam_kernel(const float *depth, const float *Kinv, const fl
         const int b = (int)(i / HW);
         const int64_t pix = i - (int64_t)b * HW;
         const float u = (float)(pix % W), v = (float)(pix / W);
-        const float *k = Kinv + (int64_t)b * 9;
-        const float c0 = k[0] * u + k[1] * v + k[2], c1 = k[3] * u + k[4] * v + k[5], c2 = k[6] * u + k[7] * v + k[8];
+        float c0[3];
+        cam_ray(Kinv + (int64_t)b * 9, u, v, c0);
         if (!BWD) {
             const float d = depth[i];
             float *o = out + (int64_t)b * 3 * HW + pix;
-            o[0] = c0 * d; o[HW] = c1 * d; o[2 * HW] = c2 * d;
+            o[0] = c0[0] * d; o[HW] = c0[1] * d; o[2 * HW] = c0[2] * d;
         } else {
             const float *g = g_cam + (int64_t)b * 3 * HW + pix;
-            out[i] = g[0] * c0 + g[HW] * c1 + g[2 * HW] * c2;
+            out[i] = g[0] * c0[0] + g[HW] * c0[1] + g[2 * HW] * c0[2];
         }
     }
 }
@@ -304,8 +294,9 @@ __global__ __launch_bounds__(256) void cam2pixel_bwd_kernel(const float *cam, co
             if (xn > 1.f || xn < -1.f) gx = 0.f;
             if (yn > 1.f || yn < -1.f) gy = 0.f;
         }
-        const float gxq = gx * 2.f / (float)(W - 1), gyq = gy * 2.f / (float)(H - 1);
-        const float gp0 = gxq / Z, gp1 = gyq / Z, gp2 = zpass ? -(gxq * xq + gyq * yq) / Z : 0.f;
+        float gp[3];
+        perspective_grad(gx * 2.f / (float)(W - 1), gy * 2.f / (float)(H - 1), xq, yq, Z, zpass, gp);
+        const float gp0 = gp[0], gp1 = gp[1], gp2 = gp[2];
         if (g_cam) {
             float *g = g_cam + (int64_t)b * 3 * HW + pix;
             g[0] = r[0] * gp0 + r[3] * gp1 + r[6] * gp2;
@@ -329,7 +320,7 @@ __global__ __launch_bounds__(256) void cam2pixel_bwd_kernel(const float *cam, co
                   (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
 }
 
-inline dim3 pix_grid(int B, int H, int W) { return dim3((W + TX - 1) / TX, (H + TY - 1) / TY, B); }
+inline dim3 smooth_grid(int N, int H, int W) { return dim3((W + SX - 1) / SX, (H + SY - 1) / SY, N); }
 
 }  // namespace
 
@@ -338,7 +329,8 @@ extern "C" {
 int64_t dvf_pose_ws_floats(int V, int B) { return (int64_t)V * B * 12; }
 
 int64_t dvf_smooth_partials_floats(int N, int H, int W) {
-    return (int64_t)((W + SX - 1) / SX) * ((H + SY - 1) / SY) * N * 4;
+    const dim3 g = smooth_grid(N, H, W);
+    return (int64_t)g.x * g.y * g.z * 4;
 }
 
 int dvf_inverse_warp_fwd(const float *img, const float *depth, const float *pose, const float *K, const float *Kinv,
@@ -426,8 +418,7 @@ int dvf_pose_vec2mat_bwd(const float *pose, const float *g_mat, float *g_pose, f
 int dvf_pixel2cam_fwd(const float *depth, const float *Kinv, float *cam, int B, int H, int W, void *stream) {
     if (!depth || !Kinv || !cam || B <= 0 || H <= 0 || W <= 0) return DVF_ERR_INVALID_ARG;
     const int64_t total = (int64_t)B * H * W;
-    const int nb = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    pixel2cam_kernel<false><<<nb, 256, 0, dvf_stream(stream)>>>(depth, Kinv, nullptr, cam, H, W, total);
+    pixel2cam_kernel<false><<<grid_stride_blocks(total), 256, 0, dvf_stream(stream)>>>(depth, Kinv, nullptr, cam, H, W, total);
     DVF_LAUNCH_CHECK();
     return DVF_OK;
 }
@@ -435,8 +426,7 @@ int dvf_pixel2cam_fwd(const float *depth, const float *Kinv, float *cam, int B, 
 int dvf_pixel2cam_bwd(const float *Kinv, const float *g_cam, float *g_depth, int B, int H, int W, void *stream) {
     if (!Kinv || !g_cam || !g_depth || B <= 0 || H <= 0 || W <= 0) return DVF_ERR_INVALID_ARG;
     const int64_t total = (int64_t)B * H * W;
-    const int nb = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    pixel2cam_kernel<true><<<nb, 256, 0, dvf_stream(stream)>>>(nullptr, Kinv, g_cam, g_depth, H, W, total);
+    pixel2cam_kernel<true><<<grid_stride_blocks(total), 256, 0, dvf_stream(stream)>>>(nullptr, Kinv, g_cam, g_depth, H, W, total);
     DVF_LAUNCH_CHECK();
     return DVF_OK;
 }
@@ -445,8 +435,7 @@ int dvf_cam2pixel_fwd(const float *cam, const float *rot, const float *tr, float
                       uint32_t flags, void *stream) {
     if (!cam || !grid || B <= 0 || H < 2 || W < 2) return DVF_ERR_INVALID_ARG;
     const int64_t total = (int64_t)B * H * W;
-    const int nb = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    cam2pixel_fwd_kernel<<<nb, 256, 0, dvf_stream(stream)>>>(cam, rot, tr, grid, H, W, (flags & DVF_PAD_BORDER) ? 0 : 1, total);
+    cam2pixel_fwd_kernel<<<grid_stride_blocks(total), 256, 0, dvf_stream(stream)>>>(cam, rot, tr, grid, H, W, (flags & DVF_PAD_BORDER) ? 0 : 1, total);
     DVF_LAUNCH_CHECK();
     return DVF_OK;
 }
@@ -475,7 +464,7 @@ int dvf_smooth_loss_fwd(const float *map, float *loss_out, float *partials, int 
                         int accumulate, void *stream) {
     if (!map || !loss_out || !partials || N <= 0 || H < 3 || W < 3 || N > 65535) return DVF_ERR_INVALID_ARG;
     hipStream_t st = dvf_stream(stream);
-    const dim3 grid((W + SX - 1) / SX, (H + SY - 1) / SY, N);
+    const dim3 grid = smooth_grid(N, H, W);
     smooth_fwd_kernel<<<grid, dim3(SX, SY), 0, st>>>(map, partials, H, W);
     DVF_LAUNCH_CHECK();
     float w[3];
@@ -491,7 +480,7 @@ int dvf_smooth_loss_bwd(const float *map, const float *grad_loss, float *g_map, 
     if (!map || !grad_loss || !g_map || N <= 0 || H < 3 || W < 3 || N > 65535) return DVF_ERR_INVALID_ARG;
     float w[3];
     smooth_weights(N, H, W, weight, w);
-    const dim3 grid((W + SX - 1) / SX, (H + SY - 1) / SY, N);
+    const dim3 grid = smooth_grid(N, H, W);
     smooth_bwd_kernel<<<grid, dim3(SX, SY), 0, dvf_stream(stream)>>>(map, grad_loss, g_map, H, W, w[0], w[1], w[2]);
     DVF_LAUNCH_CHECK();
     return DVF_OK;

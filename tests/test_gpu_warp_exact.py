@@ -10,7 +10,7 @@ Measured on the MI355X against fp64 (max-abs error / max-abs reference, maximum 
   test_inverse_warp_tolerance      depth gradient 1.4e-05   pose gradient 2.5e-06
   test_photo_loss_exact            depth gradient 5.2e-07   pose gradient 3.1e-07   loss 9.4e-08
   test_photo_loss_tolerance        depth gradient 1.2e-05   pose gradient 3.8e-07
-Source-gradient elements whose terms cancel to an exact 0 in the oracle keep a residue of at most 3.0e-07 of the maximum."""
+Source-gradient elements whose terms cancel to an exact 0 in the oracle keep a residue of at most 3.8e-07 of the maximum."""
 import functools
 
 import pytest
@@ -141,6 +141,8 @@ def _gpu_photo(case, nv, pad, align, tgt, mask, in_scale, pix=False, offset=Fals
 
 _PHOTO = [(s, nv, m, sc, c) for s in wx.EXACT_SIZES for nv in (1, 2, 4) for m in (False, True) for sc in (1.0, 0.25)
           for c in (3, 32)]
+# NV = 3 has kernel instantiations of its own: one case per size, appended so that the indices (and modes) above do not move
+_PHOTO += [(s, 3, True, 0.25, 3) for s in wx.EXACT_SIZES]
 
 
 @pytest.mark.parametrize("n,size,nv,with_mask,in_scale,c", [(i,) + p for i, p in enumerate(_PHOTO)], ids=_ids)
