@@ -124,6 +124,7 @@ struct GatherPlan {
     size_t lds;
     dim3 grid;
     int64_t ws_floats;       // split-K workspace the launch can use (0: none)
+    bool reduce_kpar;        // ... reduced by splitk_reduce_kpar_kernel: never (the plain reduce keeps this route's summation order)
 };
 
 // Plan conv_gather_kernel for one op (its classes share one launch): pure, geometry in, plan out.
@@ -197,6 +198,7 @@ int plan_gather(const ConvOp &op, GatherPlan &pl) {
     pl.MT = MT; pl.NT = NT; pl.CKH = CK / 2; pl.lds = lds_bytes(CK);
     pl.grid = dim3(a.tilesX * a.tilesY, mtiles, a.N * KS * ncls);
     pl.ws_floats = (op.covers && KS > 1) ? (int64_t)KS * a.N * a.M * a.OH * a.OW : 0;
+    pl.reduce_kpar = false;
     return DVF_OK;
 }
 
@@ -213,47 +215,22 @@ int launch_gather_ck(const GatherArgs &a, const GatherPlan &pl, hipStream_t st) 
     return DVF_OK;
 }
 
-// Launch a planned op.  With split-K (or classes that do not cover every output pixel) the blocks accumulate with atomics
-// into a zeroed output and bias + activation are applied by one finishing pass; otherwise they are fused in the epilogue.
-// Split-K over a covering class set: with a workspace the K-splits store plain partial tiles that one pass reduces in
-// fixed order (+bias, activation) -- deterministic.  *masked: the launch applied io.mask itself (else the caller runs
-// the mask pass over the finished sums).
+// Launch a planned op: output mode and finish as on the pipelined route (conv_pipe_host.h), with the plain ordered reduce.
 int run_gather(const ConvOp &op, const GatherPlan &pl, const ConvIO &io, const float *w, float *ws, int64_t ws_floats,
-               bool *masked, hipStream_t st) {
+               hipStream_t st) {
     GatherArgs a = pl.a;
     for (int s = 0; s < a.nseg; ++s) a.in[s] = io.in[s];
-    a.w = w; a.bias = io.bias;
-    float *out = io.out;
-    const bool split = !op.covers || a.KS > 1;
-    const int64_t HW = (int64_t)a.OH * a.OW, total = (int64_t)a.N * a.M * HW;
-    const bool use_ws = pl.ws_floats > 0 && ws && ws_floats >= pl.ws_floats;
-    a.out = out;
-    if (use_ws) { a.out = ws; a.ws_slice = total; a.atomic_out = 2; }
-    else {
-        if (split && hipMemsetAsync(out, 0, sizeof(float) * total, st) != hipSuccess) return DVF_ERR_LAUNCH;
-        a.atomic_out = split ? 1 : 0;
-    }
-    a.mask = a.atomic_out == 0 ? io.mask : nullptr;
-    *masked = a.mask != nullptr;
+    a.w = w; a.bias = io.bias; a.mask = io.mask;
+    int rc = prepare_output(a, out_mode_of(op.covers, a.KS, ws, ws_floats, pl.ws_floats), io.out, ws, st);
+    if (rc) return rc;
     if (const char *e = dvf_tune("DVF_DBG")) a.dbg = atoi(e);     // ablation switches for tools/conv_bench.py only
-    int rc;
     if (pl.MT == 2 && pl.NT == 2) rc = launch_gather_ck<2, 2>(a, pl, st);
     else if (pl.MT == 2) rc = launch_gather_ck<2, 1>(a, pl, st);
     else if (pl.NT == 2) rc = launch_gather_ck<1, 2>(a, pl, st);
     else rc = launch_gather_ck<1, 1>(a, pl, st);
     if (rc) return rc;
-    dvf_plan_note(DVF_K_GATHER, pl.MT, pl.NT, 1, 2 * pl.CKH, 0, a.KS, 1, 1, 256, (int)pl.lds, a.atomic_out | (a.ncls << 4));
-    const int64_t nb = (total + 255) / 256;
-    if (use_ws) {
-        splitk_reduce_kernel<<<(int)(nb > 4096 ? 4096 : nb), 256, 0, st>>>(ws, out, a.bias, a.KS, total, a.M, HW, a.act, a.alpha,
-                                                                          a.beta);
-        DVF_LAUNCH_CHECK();
-    } else if (split && (a.bias || a.act != DVF_ACT_NONE)) {
-        bias_act_kernel<<<(int)(nb > 2048 ? 2048 : nb), 256, 0, st>>>(out, a.bias, a.M, HW, total, a.act, a.alpha,
-                                                                     a.beta);
-        DVF_LAUNCH_CHECK();
-    }
-    return DVF_OK;
+    dvf_plan_note(DVF_K_GATHER, pl.MT, pl.NT, 1, 2 * pl.CKH, 0, a.KS, 1, 1, 256, (int)pl.lds, a.out_mode | (a.ncls << 4));
+    return finish_output(a, pl.reduce_kpar, ws, io.out, st);
 }
 
 // ------------------------------------------------------------------------------------- forward / dgrad routing
@@ -277,23 +254,17 @@ int fwd_unpacked(const dvf_conv_desc *d, const ConvOp &op, const ConvIO &io, con
     }
     GatherPlan pl;
     const int rc = plan_gather(op, pl);
-    bool masked;
-    return rc ? rc : run_gather(op, pl, io, w, ws, ws_floats, &masked, st);
+    return rc ? rc : run_gather(op, pl, io, w, ws, ws_floats, st);
 }
 
-// dgrad of one input segment with the unpacked weights: the head kernel for narrow segments, else conv_gather_kernel
-// (and a pass of act_bwd_kernel behind it when the launch could not apply the mask itself).
+// dgrad of one input segment with the unpacked weights: the head kernel for narrow segments, else conv_gather_kernel.
 int dgrad_unpacked(const dvf_conv_desc *d, const ConvOp &op, const ConvIO &io, const float *w, float *ws, int64_t ws_floats,
                    hipStream_t st) {
     if (dvf_head_seg_dgrad_applicable(d, op.M))
         return dvf_head_seg_dgrad(d, io.in[0], w, io.out, op.m_base, op.M, st, io.mask);     // (mask applied in the kernel)
     GatherPlan pl;
-    int rc = plan_gather(op, pl);
-    if (rc) return rc;
-    bool masked;
-    rc = run_gather(op, pl, io, w, ws, ws_floats, &masked, st);
-    if (rc || masked || !io.mask) return rc;
-    return dvf_act_bwd(io.out, io.mask, io.out, nullptr, op.N, op.M, op.OH * op.OW, DVF_ACT_RELU, 1.f, 0.f, 1, nullptr, 0, st);
+    const int rc = plan_gather(op, pl);
+    return rc ? rc : run_gather(op, pl, io, w, ws, ws_floats, st);     // (mask applied in the kernel or its finish)
 }
 
 // Split-K workspace the unpacked route of an op can use.

@@ -17,7 +17,7 @@ using dvfp::f32x16;
 using dvfp::tensor_rsrc;
 using dvfp::OOB;
 using dvfp::bload;
-using dvfp::apply_act;
+using dvfp::store_tile;
 
 struct ClassDev { int py, px, by, bx, TA, TB, OHc, OWc, tap0; };
 
@@ -36,13 +36,12 @@ struct GatherArgs {
     ClassDev cls[4];
     int act;
     float alpha, beta;
-    int KS, NCH, atomic_out, dbg;        // atomic_out 0: bias+act store, 1: atomicAdd into a zeroed output, 2: plain partial store at ks*ws_slice
+    int KS, NCH, out_mode, dbg;          // out_mode: dvfp::OutMode (conv_epilogue.h)
     int64_t ws_slice;
     int lsw, lsh, TGX, BW, BH, tilesX, tilesY;
     int PSmax, Tmax, WD; // LDS carve: patch CK*PSmax | weights Tmax*CK*COTP | wdec WD | tapB Tmax | inv 64
     int tapmap[52];      // class c uses tapmap[cls[c].tap0 + t]: class tap -> tap index of the stored kernel
-    const float *mask;   // (dgrad, atomic_out 0) ReLU backward of the producing layer: out = (mask > 0) ? v : 0; same shape as out
-    int *mask_done;      // (not read by the kernel; keeps the argument layout)
+    const float *mask;   // (dgrad) ReLU backward of the producing layer, out = (mask > 0) ? v : 0, same shape as out: applied here when OUT_FUSED, else by finish_output
 };
 
 // MT x 32 output channels, 4*NT tiles of 32 pixels per block, CK = 2*CKH reduction channels per LDS chunk.
@@ -264,80 +263,20 @@ __global__ __launch_bounds__(256) void conv_gather_kernel(const GatherArgs a) {
             }
         }
     }
-    // ---- epilogue: D[row = channel][col = pixel]; lanes 0-31 / 32-63 hold channel rows +0 / +4.  Output mode, activation
-    // and "every channel of the block exists" are launch constants: one store loop per combination (per element they cost
-    // a chain of scalar branches, an inlined sigmoid, three 64-bit multiplies and a dependent bias load each).
+    // ---- epilogue (store_tile, conv_epilogue.h): one image per block, the bias comes from global memory
     const int64_t HWo = (int64_t)a.OH * a.OW;
-    const bool full_m = m0 + 32 * MT <= a.M;
-    auto store_all = [&](auto modec, auto actc, auto fullc) __attribute__((always_inline)) {
-        constexpr int MODE = decltype(modec)::value, ACT = decltype(actc)::value;
-        constexpr bool FULL = decltype(fullc)::value;
-        float bv[MT][16];
-        if constexpr (MODE == 0) {
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int mm = m0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                    bv[m][r] = (a.bias && mm < a.M) ? a.bias[mm] : 0.f;        // (all loads in flight together)
-                }
-        }
-        float *obase = a.out + (MODE == 2 ? (int64_t)ks * a.ws_slice : 0) + ((int64_t)n * a.M + m0 + 4 * kh) * HWo;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
+    store_tile<MT, NT>(
+        acc, a.out + (a.out_mode == dvfp::OUT_WS ? (int64_t)ks * a.ws_slice : 0), a.mask, a.out_mode, a.act, a.alpha, a.beta, m0, kh, a.M, HWo,
+        [&](int i, int64_t &off) __attribute__((always_inline)) {
             const int oy = oy0 + opy[i], ox = ox0 + opx[i];
             const int Y = oy * a.OS + c.py, X = ox * a.OS + c.px;
-            const bool pok = (oy < c.OHc) && (ox < c.OWc) && (Y < a.OH) && (X < a.OW);
-            float *pbase = obase + (int64_t)Y * a.OW + X;
-            float mk[MT][16];
-            if constexpr (MODE == 3) {           // all mask loads of the tile first (invalid elements read element 0)
-#pragma unroll
-                for (int m = 0; m < MT; ++m)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int ml = m * 32 + (r & 3) + 8 * (r >> 2);
-                        const bool ok = pok && (FULL || m0 + 4 * kh + ml < a.M);
-                        mk[m][r] = a.mask[ok ? (pbase - a.out) + (int64_t)ml * HWo : 0];
-                    }
-            }
-            if (pok) {
-#pragma unroll
-                for (int m = 0; m < MT; ++m) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int ml = m * 32 + (r & 3) + 8 * (r >> 2);
-                        if (FULL || m0 + 4 * kh + ml < a.M) {
-                            float *op = pbase + (int64_t)ml * HWo;          // (ml * HWo: scalar)
-                            const float v = acc[m][i][r];
-                            if constexpr (MODE == 3) {                   // dgrad + ReLU backward of the producing layer
-                                *op = mk[m][r] > 0.f ? v : 0.f;
-                            } else if constexpr (MODE == 0) {
-                                const float t = v + bv[m][r];
-                                if constexpr (ACT == DVF_ACT_RELU) *op = fmaxf(t, 0.f);
-                                else if constexpr (ACT == DVF_ACT_SIGMOID_AFFINE) *op = a.alpha * (1.f / (1.f + expf(-t))) + a.beta;
-                                else *op = t;
-                            } else if constexpr (MODE == 1) {
-                                atomicAdd(op, v);
-                            } else {
-                                *op = v;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-    };
-    using std::integral_constant;
-    auto by_full = [&](auto modec, auto actc) __attribute__((always_inline)) {
-        if (full_m) store_all(modec, actc, std::true_type{});
-        else store_all(modec, actc, std::false_type{});
-    };
-    if (a.atomic_out == 0 && a.mask) by_full(integral_constant<int, 3>{}, integral_constant<int, DVF_ACT_NONE>{});
-    else if (a.atomic_out == 2) by_full(integral_constant<int, 2>{}, integral_constant<int, DVF_ACT_NONE>{});
-    else if (a.atomic_out == 1) by_full(integral_constant<int, 1>{}, integral_constant<int, DVF_ACT_NONE>{});
-    else if (a.act == DVF_ACT_RELU) by_full(integral_constant<int, 0>{}, integral_constant<int, DVF_ACT_RELU>{});
-    else if (a.act == DVF_ACT_SIGMOID_AFFINE) by_full(integral_constant<int, 0>{}, integral_constant<int, DVF_ACT_SIGMOID_AFFINE>{});
-    else by_full(integral_constant<int, 0>{}, integral_constant<int, DVF_ACT_NONE>{});
+            off = ((int64_t)n * a.M + m0 + 4 * kh) * HWo + (int64_t)Y * a.OW + X;
+            return (oy < c.OHc) && (ox < c.OWc) && (Y < a.OH) && (X < a.OW);
+        },
+        [&](int ml) __attribute__((always_inline)) {
+            const int mm = m0 + ml + 4 * kh;
+            return (a.bias && mm < a.M) ? a.bias[mm] : 0.f;
+        });
 }
 
 }  // namespace

@@ -3,19 +3,16 @@
 // layers; they are memory-bound (read the C_in-channel activation once), so plain FMAs over an LDS-staged tile are
 // the right tool: forward, dgrad and wgrad.  3x3, stride 1, padding 1, single input segment, C_out <= 4.
 #include "conv_head.h"
+#include "conv_epilogue.h"
 
 namespace {
+
+using dvfp::apply_act;
 
 constexpr int HT_W = 64, HT_H = 4;          // pixel tile per block (256 threads, one pixel each)
 constexpr int HP_W = HT_W + 2, HP_H = HT_H + 2;
 constexpr int HCK = 8;                      // input channels staged per pass (forward)
 constexpr int HWK = 7;                      // ... in wgrad: 7 channels x 9 taps = 63 columns, one per lane
-
-__device__ __forceinline__ float head_act(float v, int act, float alpha, float beta) {
-    if (act == DVF_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == DVF_ACT_SIGMOID_AFFINE) return alpha * (1.f / (1.f + expf(-v))) + beta;
-    return v;
-}
 
 // stage `nch` channel planes (tile + halo 1, zero outside the image) into lds[ch][HP_H][HP_W]
 __device__ __forceinline__ void stage_tile(float *lds, const float *__restrict__ src, int64_t plane, int nch, int H, int W,
@@ -25,6 +22,20 @@ __device__ __forceinline__ void stage_tile(float *lds, const float *__restrict__
         const int y = y0 + py - 1, x = x0 + px - 1;
         lds[e] = (y >= 0 && y < H && x >= 0 && x < W) ? src[ch * plane + (int64_t)y * W + x] : 0.f;
     }
+}
+
+// The nine taps of one input channel: acc[r][m] += wk(m, k) * v[k / 3 + r][k % 3] over the channel's neighbourhood v (ROWS
+// output rows + halo), in the order m, k, r.
+template <int ROWS, int MO, class WK>
+__device__ __forceinline__ void taps9(const float (&v)[ROWS + 2][3], WK wk, float (&acc)[ROWS][MO]) {
+#pragma unroll
+    for (int m = 0; m < MO; ++m)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const float w = wk(m, k);
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) acc[r][m] = fmaf(w, v[k / 3 + r][k % 3], acc[r][m]);
+        }
 }
 
 // out[n][mo][y][x] = act(b[mo] + sum_c sum_taps w[mo][c][tap] * in[n][c][y+ta-1][x+tb-1])
@@ -102,9 +113,19 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const HeadSegs in, const 
             }
         __syncthreads();
         if (sg2 < in.n) issue(sg2, cs2);
+        auto hood = [&](int ch, float (&v)[ROWS + 2][3]) __attribute__((always_inline)) {     // neighbourhood of this thread's pixels
+            const float *t = tile + ch * FPN + ly * HP_W + lx;
+#pragma unroll
+            for (int a = 0; a < ROWS + 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 3; ++b) v[a][b] = t[a * HP_W + b];
+        };
         // (1-4 channel heads) four input channels in flight with their own accumulators: a thread's work is one long
         // chain of LDS reads and dependent FMAs (288 per 32-channel round), and these layers run a block or less per CU
         if constexpr (MO != 16) {
+            auto wlds = [&](int c) __attribute__((always_inline)) {           // LDS broadcast reads
+                return [=](int m, int k) __attribute__((always_inline)) { return wsh[(m * C + c) * 9 + k]; };
+            };
             float part[3][ROWS][MO];
 #pragma unroll
             for (int q = 0; q < 3; ++q)
@@ -116,13 +137,8 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const HeadSegs in, const 
             for (; ch + 4 <= nch; ch += 4) {
                 float v4[4][ROWS + 2][3];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float *t = tile + (ch + q) * FPN + ly * HP_W + lx;
-#pragma unroll
-                    for (int a = 0; a < ROWS + 2; ++a)
-#pragma unroll
-                        for (int b = 0; b < 3; ++b) v4[q][a][b] = t[a * HP_W + b];
-                }
+                for (int q = 0; q < 4; ++q) hood(ch + q, v4[q]);
+                // (own copy of taps9: through the helper head_fwd_kernel<4, 8, 8> takes 222 VGPRs instead of 156, 2 waves per SIMD for 3)
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -140,54 +156,24 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const HeadSegs in, const 
                     }
             }
             for (; ch < nch; ++ch) {
-                const float *t = tile + ch * FPN + ly * HP_W + lx;
-#pragma unroll
-                for (int m = 0; m < MO; ++m) {
-                    const float *wm = wsh + (m * C + cg + ch) * 9;
-#pragma unroll
-                    for (int k = 0; k < 9; ++k)
-#pragma unroll
-                        for (int r = 0; r < ROWS; ++r) acc[r][m] = fmaf(wm[k], t[(k / 3 + r) * HP_W + k % 3], acc[r][m]);
-                }
+                float v[ROWS + 2][3];
+                hood(ch, v);
+                taps9<ROWS, MO>(v, wlds(cg + ch), acc);
             }
 #pragma unroll
             for (int r = 0; r < ROWS; ++r)
 #pragma unroll
                 for (int m = 0; m < MO; ++m) acc[r][m] += (part[0][r][m] + part[1][r][m]) + part[2][r][m];
-        }
-        for (int ch = 0; ch < (MO == 16 ? nch : 0); ++ch) {
-            const float *t = tile + ch * FPN + ly * HP_W + lx;
-            float v[ROWS + 2][3];
-#pragma unroll
-            for (int a = 0; a < ROWS + 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 3; ++b) v[a][b] = t[a * HP_W + b];
-            if constexpr (MO == 16) {
+        } else {
+            for (int ch = 0; ch < nch; ++ch) {
+                float v[ROWS + 2][3];
+                hood(ch, v);
                 typedef float f4h __attribute__((ext_vector_type(4)));
                 const f4h *wq = reinterpret_cast<const f4h *>(wsh + (cg + ch) * (MO * 9));     // 16-byte aligned: 144 floats per channel
                 f4h wr[MO * 9 / 4];
 #pragma unroll
                 for (int q = 0; q < MO * 9 / 4; ++q) wr[q] = wq[q];
-#pragma unroll
-                for (int m = 0; m < MO; ++m)
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) {
-                        const int f = m * 9 + k;
-                        const float wk = wr[f >> 2][f & 3];
-#pragma unroll
-                        for (int r = 0; r < ROWS; ++r) acc[r][m] = fmaf(wk, v[k / 3 + r][k % 3], acc[r][m]);
-                    }
-            } else {
-#pragma unroll
-                for (int m = 0; m < MO; ++m) {
-                    const float *wm = wsh + (m * C + cg + ch) * 9;             // LDS broadcast reads
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) {
-                        const float wk = wm[k];
-#pragma unroll
-                        for (int r = 0; r < ROWS; ++r) acc[r][m] = fmaf(wk, v[k / 3 + r][k % 3], acc[r][m]);
-                    }
-                }
+                taps9<ROWS, MO>(v, [&](int m, int k) __attribute__((always_inline)) { return wr[(m * 9 + k) >> 2][(m * 9 + k) & 3]; }, acc);
             }
         }
         cg += nch; sg = sg2; cs = cs2;
@@ -206,7 +192,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const HeadSegs in, const 
             } else {
 #pragma unroll
                 for (int m = 0; m < MO; ++m)
-                    out[((int64_t)n * MO + m) * plane + (int64_t)y * W + x] = head_act(acc[r][m], act, alpha, beta);
+                    out[((int64_t)n * MO + m) * plane + (int64_t)y * W + x] = apply_act(acc[r][m], act, alpha, beta);
             }
         }
     }
@@ -407,7 +393,7 @@ __global__ __launch_bounds__(256) void dconvt_s2_fwd_kernel(const float *__restr
         const int X = 2 * x;
 #pragma unroll
         for (int co = 0; co < CO; ++co) {
-            float r0 = head_act(acc[dy][0][co], act, alpha, beta), r1 = head_act(acc[dy][1][co], act, alpha, beta);
+            float r0 = apply_act(acc[dy][0][co], act, alpha, beta), r1 = apply_act(acc[dy][1][co], act, alpha, beta);
             float *q = op + co * oplane + (int64_t)Y * OW + X;
             if (X + 1 < OW && (OW & 1) == 0) {
                 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -420,8 +406,6 @@ __global__ __launch_bounds__(256) void dconvt_s2_fwd_kernel(const float *__restr
         }
     }
 }
-
-inline int cdivh(int a, int b) { return (a + b - 1) / b; }
 
 }  // namespace
 
@@ -454,7 +438,7 @@ bool dvf_dconvt_applicable(const dvf_conv_desc *d, int nseg) {
 }
 
 int dvf_dconvt_fwd(const dvf_conv_desc *d, const float *in, const float *w, const float *bias, float *out, hipStream_t st) {
-    const dim3 grid(cdivh(d->W_in, 64), cdivh(d->H_in, 4), d->N);
+    const dim3 grid(cdiv(d->W_in, 64), cdiv(d->H_in, 4), d->N);
     const size_t lds = (size_t)d->C_in * d->C_out * d->KH * d->KW * 4;
     if ((reinterpret_cast<uintptr_t>(w) & 15) != 0 || lds > 64 * 1024) return DVF_ERR_UNSUPPORTED;
 #define DCONVT(CO, K) dconvt_s2_fwd_kernel<CO, K><<<grid, 256, lds, st>>>(in, w, bias, out, d->C_in, d->H_in, d->W_in, d->H_out, d->W_out, d->act, d->alpha, d->beta)
@@ -466,22 +450,10 @@ int dvf_dconvt_fwd(const dvf_conv_desc *d, const float *in, const float *w, cons
     return DVF_OK;
 }
 
-#define HEAD_DISPATCH(MOV, CALL)                 \
+#define HEAD_CASE(N, ...) case N: { constexpr int MO = N; __VA_ARGS__; } break;
+#define HEAD_DISPATCH(MOV, CALL, ...)            /* (...: further cases) */ \
     switch (MOV) {                               \
-        case 1: { constexpr int MO = 1; CALL; } break; \
-        case 2: { constexpr int MO = 2; CALL; } break; \
-        case 3: { constexpr int MO = 3; CALL; } break; \
-        case 4: { constexpr int MO = 4; CALL; } break; \
-        default: return DVF_ERR_UNSUPPORTED;     \
-    }
-
-#define HEAD_FWD_DISPATCH(MOV, CALL)             \
-    switch (MOV) {                               \
-        case 1: { constexpr int MO = 1; CALL; } break; \
-        case 2: { constexpr int MO = 2; CALL; } break; \
-        case 3: { constexpr int MO = 3; CALL; } break; \
-        case 4: { constexpr int MO = 4; CALL; } break; \
-        case 16: { constexpr int MO = 16; CALL; } break; \
+        HEAD_CASE(1, CALL) HEAD_CASE(2, CALL) HEAD_CASE(3, CALL) HEAD_CASE(4, CALL) __VA_ARGS__ \
         default: return DVF_ERR_UNSUPPORTED;     \
     }
 
@@ -490,7 +462,7 @@ static int head_fwd_launch(int MOv, const HeadSegs &in, const float *w, const fl
                            int act, float alpha, float beta, int ws_m, int ws_c, int flip, const float *mask, hipStream_t st) {
     const bool lowres = (int64_t)N * H * W <= (int64_t)4 * 64 * 208 && MOv <= 4 && C >= 32;
     const int FTH = lowres ? 4 : FT_H, HCKT = lowres ? 32 : HCK;
-    const int tilesX = cdivh(W, HT_W), tilesY = cdivh(H, FTH);
+    const int tilesX = cdiv(W, HT_W), tilesY = cdiv(H, FTH);
     const dim3 grid(tilesX * tilesY, N);
     const size_t lds = ((size_t)((MOv * C * 9 + 3) & ~3) + (size_t)HCKT * (FTH + 2) * HP_W) * 4;
 #define HEAD_FWD_GO(HC, FH) head_fwd_kernel<MO, HC, FH><<<grid, 256, lds, st>>>(in, w, bias, out, C, H, W, tilesX, act, alpha, beta, ws_m, ws_c, flip, mask)
@@ -503,7 +475,7 @@ static int head_fwd_launch(int MOv, const HeadSegs &in, const float *w, const fl
             }
             HEAD_FWD_GO(32, 4); });
     } else {
-        HEAD_FWD_DISPATCH(MOv, (HEAD_FWD_GO(8, 8)));
+        HEAD_DISPATCH(MOv, (HEAD_FWD_GO(8, 8)), HEAD_CASE(16, (HEAD_FWD_GO(8, 8))));
     }
 #undef HEAD_FWD_GO
     DVF_LAUNCH_CHECK();
@@ -560,7 +532,7 @@ int dvf_head_seg_dgrad(const dvf_conv_desc *d, const float *dpre, const float *w
 }
 
 int dvf_head_dgrad(const dvf_conv_desc *d, const float *dpre, const float *w, float *din, hipStream_t st, const float *mask) {
-    const int tilesX = cdivh(d->W_in, HT_W), tilesY = cdivh(d->H_in, HT_H);
+    const int tilesX = cdiv(d->W_in, HT_W), tilesY = cdiv(d->H_in, HT_H);
     const dim3 grid(tilesX * tilesY, d->N);
     HEAD_DISPATCH(d->C_out, (head_dgrad_kernel<MO><<<grid, 256, (size_t)d->C_in * ((MO * 9 + 3) & ~3) * 4, st>>>(
                                 dpre, w, din, d->C_in, d->H_in, d->W_in, tilesX, mask)));
@@ -570,8 +542,8 @@ int dvf_head_dgrad(const dvf_conv_desc *d, const float *dpre, const float *w, fl
 }
 
 static void head_wgrad_grid(const dvf_conv_desc *d, int &tilesX, int &tilesY, int &chunks, int &groups) {
-    tilesX = cdivh(d->W_in, HT_W); tilesY = cdivh(d->H_in, HT_H);
-    chunks = cdivh(d->C_in, HWK);
+    tilesX = cdiv(d->W_in, HT_W); tilesY = cdiv(d->H_in, HT_H);
+    chunks = cdiv(d->C_in, HWK);
     const int ntiles = d->N * tilesX * tilesY;
     groups = 2048 / chunks;
     if (groups < 1) groups = 1;

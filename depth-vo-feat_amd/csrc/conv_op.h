@@ -7,7 +7,6 @@
 namespace {
 
 inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int roundup(int v, int q) { return (v + q - 1) / q * q; }
 
 // One class of output pixels (oy*OS+py, ox*OS+px) that read the input pixels (oy*IS+by+ta, ox*IS+bx+tb), ta < TA, tb < TB;

@@ -18,6 +18,7 @@
 // The inner loop is organised in UNITS of one kernel row (TBU taps) x VW channel pairs with no branches inside a unit.
 #pragma once
 #include "dvf_common.h"
+#include "conv_epilogue.h"
 
 namespace dvfp {
 
@@ -32,7 +33,6 @@ namespace dvfp {
 #define DVF_STAMPS_ON 0
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 
 // Raw buffer descriptor over a whole tensor, built from wave-uniform values (readfirstlane keeps hipcc from
@@ -50,12 +50,6 @@ __device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, unsigned voff, 
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
 
-__device__ __forceinline__ float apply_act(float v, int act, float alpha, float beta) {
-    if (act == DVF_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == DVF_ACT_SIGMOID_AFFINE) return alpha * (1.f / (1.f + expf(-v))) + beta;
-    return v;
-}
-
 struct PClass { int py, px, by, bx, TA, TB, OHc, OWc, SL, NTG; unsigned wp_off; };   // SL: slab floats; wp_off: floats
 
 struct PipeArgs {
@@ -64,13 +58,13 @@ struct PipeArgs {
     int nseg;
     const float *wp;         // packed weights of this launch
     const float *bias;
-    float *out;              // [N, M, OH, OW]  (or the split-K workspace [KS][N, M, OH, OW] when out_mode == 2)
+    float *out;              // [N, M, OH, OW]  (or the split-K workspace [KS][N, M, OH, OW] when out_mode == OUT_WS)
     int M, N, IH, IW, OH, OW;
     int OS, IS, ncls;
     PClass cls[4];
     int act;
     float alpha, beta;
-    int KS, NCH, out_mode, NG;            // out_mode 0: bias+act store, 1: atomicAdd, 2: plain partial store at ks*ws_slice
+    int KS, NCH, out_mode, NG;            // out_mode: OutMode (conv_epilogue.h)
     int64_t ws_slice;
     int lsw, lsh, TGX, TGY, BW, BH, BN, tilesX, tilesY;
     int x4;                               // patch DMA in 16-byte lanes (see pipe_geo)
@@ -78,7 +72,7 @@ struct PipeArgs {
     int SLmax, PSRmax, NST;               // LDS carve per stage (NST = 2 or 3 stages): SLmax weight floats | CK * PSRmax patch floats
     int dbg;                              // ablation switches (tools/conv_bench.py): 1 no patch loads, 2 no weight loads, 4 no MFMA
     unsigned long long *stamps;           // -DDVF_TUNING builds: per-block cycle account (8 x u64 per block), or NULL
-    // dgrad of a segment produced by a ReLU layer (out_mode 0): out = (mask > 0) ? v : 0 -- the activation backward pass
+    // dgrad of a segment produced by a ReLU layer (OUT_FUSED): out = (mask > 0) ? v : 0 -- the activation backward pass
     // of the PRODUCING layer, done where its gradient is born
     const float *mask;                    // same shape as out (the producing layer's output), or NULL
 };
@@ -380,7 +374,7 @@ __global__ __launch_bounds__(PIPE_THREADS_4P) void conv_pipe_kernel(const PipeAr
     float *bias_lds = smem + a.NST * stage_floats;
     if (tid < 32 * MTW) {
         const int mm = mb * (32 * MTW) + tid;
-        bias_lds[tid] = (a.bias && a.out_mode == 0 && mm < a.M) ? a.bias[mm] : 0.f;
+        bias_lds[tid] = (a.bias && a.out_mode == OUT_FUSED && mm < a.M) ? a.bias[mm] : 0.f;
     }
     const int NU = c.NTG * CPG;                            // units per chunk
     int opy[NT], opx[NT], opn[NT];
@@ -580,20 +574,20 @@ __global__ __launch_bounds__(PIPE_THREADS_4P) void conv_pipe_kernel(const PipeAr
             }
         }
     };
-    // ---- epilogue: D[row = channel][col = pixel]; lanes 0-31 / 32-63 hold channel rows +0 / +4
+    // ---- epilogue (store_tile, conv_epilogue.h): the batch is folded into the tile, the bias waits in LDS
     if DVF_DBG(a, 16) { stamp_out(); return; }
     const int m0 = mb * (32 * MTW) + wm * (32 * MT);
-    float *outp = a.out + (a.out_mode == 2 ? (int64_t)ks * a.ws_slice : 0);
     const int64_t HW = (int64_t)a.OH * a.OW;
-    if (a.mask && a.out_mode == 0) {
-        // ReLU backward of the producing layer (no bias / activation of this op: it is a dgrad)
+    if (a.mask && a.out_mode == OUT_FUSED) {
+        // ReLU backward of the producing layer (no bias / activation of this op: it is a dgrad).  Own copy of store_tile's
+        // MODE 3: through the shared loop hipcc allocates 155 VGPRs for every instantiation (141 / 153 with this one)
+        float *outp = a.out;
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
             const int oy = oy0 + opy[i], ox = ox0 + opx[i], n = n0 + opn[i];
             const int Y = oy * a.OS + c.py, X = ox * a.OS + c.px;
             const bool pok = (oy < c.OHc) && (ox < c.OWc) && (Y < a.OH) && (X < a.OW) && (opn[i] < a.BN) && (n < a.N);
             const int64_t base = ((int64_t)n * a.M + m0 + 4 * kh) * HW + (int64_t)Y * a.OW + X;
-            // all mask loads of the tile first (no branch around them: invalid elements read element 0), then the stores
             float mk[MT][16];
 #pragma unroll
             for (int m = 0; m < MT; ++m)
@@ -617,61 +611,15 @@ __global__ __launch_bounds__(PIPE_THREADS_4P) void conv_pipe_kernel(const PipeAr
         stamp_out();
         return;
     }
-    // The output mode, the activation and "every channel of this wave exists" are launch constants: the store loops are
-    // instantiated per combination (evaluating them per element cost 30+ scalar branches and an inlined sigmoid in every
-    // one of the 16*MT*NT stores of a lane -- microseconds per block), rows are reached by scalar multiples of HW.
-    const bool full_m = m0 + 32 * MT <= a.M;
-    auto store_all = [&](auto modec, auto actc, auto fullc) __attribute__((always_inline)) {
-        constexpr int MODE = decltype(modec)::value, ACT = decltype(actc)::value;
-        constexpr bool FULL = decltype(fullc)::value;
-        float bv[MT][16];
-        if constexpr (MODE == 0) {
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) bv[m][r] = bias_lds[wm * (32 * MT) + 4 * kh + m * 32 + (r & 3) + 8 * (r >> 2)];
-        }
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
+    store_tile<MT, NT>(
+        acc, a.out + (a.out_mode == OUT_WS ? (int64_t)ks * a.ws_slice : 0), nullptr, a.out_mode, a.act, a.alpha, a.beta, m0, kh, a.M, HW,
+        [&](int i, int64_t &off) __attribute__((always_inline)) {
             const int oy = oy0 + opy[i], ox = ox0 + opx[i], n = n0 + opn[i];
             const int Y = oy * a.OS + c.py, X = ox * a.OS + c.px;
-            const bool pok = (oy < c.OHc) && (ox < c.OWc) && (Y < a.OH) && (X < a.OW) && (opn[i] < a.BN) && (n < a.N);
-            float *pbase = outp + ((int64_t)n * a.M + m0 + 4 * kh) * HW + (int64_t)Y * a.OW + X;
-            if (pok) {
-#pragma unroll
-                for (int m = 0; m < MT; ++m) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int ml = m * 32 + (r & 3) + 8 * (r >> 2);
-                        if (FULL || m0 + 4 * kh + ml < a.M) {
-                            float *op = pbase + (int64_t)ml * HW;      // (ml * HW: scalar)
-                            const float v = acc[m][i][r];
-                            if constexpr (MODE == 0) {
-                                const float t = v + bv[m][r];
-                                if constexpr (ACT == DVF_ACT_RELU) *op = fmaxf(t, 0.f);
-                                else if constexpr (ACT == DVF_ACT_SIGMOID_AFFINE) *op = a.alpha * (1.f / (1.f + expf(-t))) + a.beta;
-                                else *op = t;
-                            } else if constexpr (MODE == 1) {
-                                atomicAdd(op, v);
-                            } else {
-                                *op = v;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-    };
-    using std::integral_constant;
-    auto by_full = [&](auto modec, auto actc) __attribute__((always_inline)) {
-        if (full_m) store_all(modec, actc, std::true_type{});
-        else store_all(modec, actc, std::false_type{});
-    };
-    if (a.out_mode == 2) by_full(integral_constant<int, 2>{}, integral_constant<int, DVF_ACT_NONE>{});
-    else if (a.out_mode == 1) by_full(integral_constant<int, 1>{}, integral_constant<int, DVF_ACT_NONE>{});
-    else if (a.act == DVF_ACT_RELU) by_full(integral_constant<int, 0>{}, integral_constant<int, DVF_ACT_RELU>{});
-    else if (a.act == DVF_ACT_SIGMOID_AFFINE) by_full(integral_constant<int, 0>{}, integral_constant<int, DVF_ACT_SIGMOID_AFFINE>{});
-    else by_full(integral_constant<int, 0>{}, integral_constant<int, DVF_ACT_NONE>{});
+            off = ((int64_t)n * a.M + m0 + 4 * kh) * HW + (int64_t)Y * a.OW + X;
+            return (oy < c.OHc) && (ox < c.OWc) && (Y < a.OH) && (X < a.OW) && (opn[i] < a.BN) && (n < a.N);
+        },
+        [&](int ml) __attribute__((always_inline)) { return bias_lds[wm * (32 * MT) + 4 * kh + ml]; });
     stamp_out();
 }
 

@@ -1,5 +1,5 @@
-// Host side of the pipelined convolution (conv.hip): weight packing, the finishing passes of a split launch, planning
-// and launch.
+// Host side of the pipelined convolution (conv.hip): weight packing, planning and launch; and what it shares with the
+// gather route: the output mode of a launch and the passes that finish a split one.
 #pragma once
 #include <string.h>
 #include "dvf_common.h"
@@ -13,6 +13,9 @@ using dvfp::PipeArgs;
 using dvfp::PipeGeo;
 using dvfp::pipe_geo;
 using dvfp::PIPE_MAXNPI;
+using dvfp::OUT_FUSED;
+using dvfp::OUT_ATOMIC;
+using dvfp::OUT_WS;
 
 // ------------------------------------------------------------------------------------------------ weight packing
 struct alignas(8) PackArgsBody {
@@ -234,6 +237,55 @@ __global__ __launch_bounds__(256) void splitk_reduce_kpar_kernel(const float *ws
     out[i] = dvfp::apply_act(v, act, alpha, beta);
 }
 
+// ---------------------------------------------------------------- output mode and finish (both routes: Args = PipeArgs / GatherArgs)
+// Classes that do not cover every output pixel, and K-splits without a workspace, accumulate with float atomics into a
+// zeroed output; K-splits with a workspace (plan_ws_floats floats) store plain partial tiles that one pass reduces in a
+// fixed order: deterministic.
+inline int out_mode_of(bool covers, int KS, const float *ws, int64_t ws_floats, int64_t plan_ws_floats) {
+    if (!covers) return OUT_ATOMIC;
+    if (KS <= 1) return OUT_FUSED;
+    return (ws && ws_floats >= plan_ws_floats) ? OUT_WS : OUT_ATOMIC;
+}
+
+// Point the launch at what its blocks write: the output (zeroed first for atomics) or the workspace.
+template <class Args>
+int prepare_output(Args &a, int mode, float *out, float *ws, hipStream_t st) {
+    const int64_t total = (int64_t)a.N * a.M * a.OH * a.OW;
+    a.out_mode = mode;
+    a.out = out;
+    if (mode == OUT_WS) { a.out = ws; a.ws_slice = total; }
+    if (mode == OUT_ATOMIC && hipMemsetAsync(out, 0, sizeof(float) * total, st) != hipSuccess) return DVF_ERR_LAUNCH;
+    return DVF_OK;
+}
+
+// What follows the main kernel of a split launch: the reduction of the partial tiles (kpar: by splitk_reduce_kpar_kernel,
+// a choice of the plan) with bias, activation or a dgrad's ReLU mask; or, after atomics, bias + activation and the mask pass.
+template <class Args>
+int finish_output(const Args &a, bool kpar, const float *ws, float *out, hipStream_t st) {
+    const int64_t HW = (int64_t)a.OH * a.OW, total = (int64_t)a.N * a.M * HW, nb = (total + 255) / 256;
+    if (a.out_mode == OUT_WS && kpar) {
+        splitk_reduce_kpar_kernel<<<(unsigned)((total + 63) / 64), 256, 0, st>>>(ws, out, a.bias, a.mask, a.KS, total, a.M, (int)HW,
+                                                                                a.act, a.alpha, a.beta);
+        DVF_LAUNCH_CHECK();
+    } else if (a.out_mode == OUT_WS && a.mask) {
+        int chunks = 1;
+        const int64_t planes = (int64_t)a.N * a.M;
+        while (planes * chunks < 1024 && HW / (chunks * 2) >= 256) chunks *= 2;
+        splitk_reduce_mask_kernel<<<(unsigned)(planes * chunks), 256, 0, st>>>(ws, out, a.mask, a.KS, total, (int)HW, chunks);
+        DVF_LAUNCH_CHECK();
+    } else if (a.out_mode == OUT_WS) {
+        splitk_reduce_kernel<<<(int)(nb > 4096 ? 4096 : nb), 256, 0, st>>>(ws, out, a.bias, a.KS, total, a.M, HW, a.act,
+                                                                          a.alpha, a.beta);
+        DVF_LAUNCH_CHECK();
+    } else if (a.out_mode == OUT_ATOMIC && (a.bias || a.act != DVF_ACT_NONE)) {
+        bias_act_kernel<<<(int)(nb > 2048 ? 2048 : nb), 256, 0, st>>>(out, a.bias, a.M, HW, total, a.act, a.alpha, a.beta);
+        DVF_LAUNCH_CHECK();
+    }
+    if (a.out_mode == OUT_ATOMIC && a.mask)     // the mask pass runs over the finished sums
+        return dvf_act_bwd(out, a.mask, out, nullptr, a.N, a.M, (int)HW, DVF_ACT_RELU, 1.f, 0.f, 1, nullptr, 0, st);
+    return DVF_OK;
+}
+
 #ifdef DVF_TUNING
 constexpr size_t STAMP_MAX_BLOCKS = 16384;
 unsigned long long *g_stamp_buf = nullptr;
@@ -247,6 +299,7 @@ struct PipePlan {
     dim3 grid;
     int64_t packed_floats;   // the op's share of the packed-weight buffer
     int64_t ws_floats;       // split-K workspace the launch can use (0: none)
+    bool reduce_kpar;        // ... reduced by splitk_reduce_kpar_kernel
     size_t pack_lds;         // LDS tile of the packing kernel
 };
 
@@ -428,6 +481,7 @@ int plan_pipe(const ConvOp &op, PipePlan &pl) {
     if ((int64_t)a.NG * KS * ncls > 65535) return DVF_ERR_UNSUPPORTED;
     a.KS = KS;
     pl.ws_floats = (op.covers && KS > 1) ? (int64_t)KS * a.N * a.M * a.OH * a.OW : 0;
+    pl.reduce_kpar = KS >= 8 && (int64_t)a.OH * a.OW < ((int64_t)1 << 30);
     for (int s2 = 0; s2 < a.nseg; ++s2)
         if ((int64_t)a.N * a.segC[s2] * a.IH * a.IW * 4 >= ((int64_t)1 << 31) - 16) return DVF_ERR_UNSUPPORTED;
     pl.MT = MT; pl.NT = NT; pl.WM = WM; pl.CKH = CK / 2; pl.TBU = TBU; pl.lds = dd.lds;
@@ -490,15 +544,9 @@ int run_pipe(const ConvOp &op, const PipePlan &pl, const ConvIO &io, const float
         if (a.x4 && (reinterpret_cast<uintptr_t>(a.in[s]) & 15)) return DVF_ERR_UNSUPPORTED;    // (a view at an odd element offset)
     }
     a.wp = packed; a.bias = io.bias; a.mask = io.mask;
-    float *out = io.out;
-    const int64_t HW = (int64_t)a.OH * a.OW, total = (int64_t)a.N * a.M * HW;
-    int mode = 0;
-    if (!op.covers) mode = 1;
-    else if (a.KS > 1) mode = (ws && ws_floats >= pl.ws_floats) ? 2 : 1;
-    if (mode == 1 && hipMemsetAsync(out, 0, sizeof(float) * total, st) != hipSuccess) return DVF_ERR_LAUNCH;
-    a.out_mode = mode;
-    a.out = out;
-    if (mode == 2) { a.out = ws; a.ws_slice = total; }
+    const int mode = out_mode_of(op.covers, a.KS, ws, ws_floats, pl.ws_floats);
+    int rc = prepare_output(a, mode, io.out, ws, st);
+    if (rc) return rc;
     if (const char *e = dvf_tune("DVF_DBG")) a.dbg = atoi(e);
     a.stamps = nullptr;
 #ifdef DVF_TUNING
@@ -517,30 +565,8 @@ int run_pipe(const ConvOp &op, const PipePlan &pl, const ConvIO &io, const float
         fprintf(stderr, "[pipe] M %d chunks %d N %d out %dx%d cls %d | MT %d NT %d WM %d CK %d TBU %d KS %d BN %d tile %dx%d "
                 "(sub %dx%d) grid %ux%ux%u lds %zu x%d mode %d\n", a.M, a.NCH, a.N, a.OH, a.OW, a.ncls, pl.MT, pl.NT, pl.WM,
                 2 * pl.CKH, pl.TBU, a.KS, a.BN, a.BH, a.BW, 1 << a.lsh, 1 << a.lsw, pl.grid.x, pl.grid.y, pl.grid.z, pl.lds, a.NST, mode);
-    int rc = launch_pipe(a, pl, st);
-    if (rc) return rc;
-    const int64_t nb = (total + 255) / 256;
-    if (mode == 2 && a.KS >= 8 && HW < ((int64_t)1 << 30)) {
-        splitk_reduce_kpar_kernel<<<(unsigned)((total + 63) / 64), 256, 0, st>>>(ws, out, a.bias, a.mask, a.KS, total, a.M, (int)HW,
-                                                                                a.act, a.alpha, a.beta);
-        DVF_LAUNCH_CHECK();
-    } else if (mode == 2 && a.mask) {
-        int chunks = 1;
-        const int64_t planes = (int64_t)a.N * a.M;
-        while (planes * chunks < 1024 && HW / (chunks * 2) >= 256) chunks *= 2;
-        splitk_reduce_mask_kernel<<<(unsigned)(planes * chunks), 256, 0, st>>>(ws, out, a.mask, a.KS, total, (int)HW, chunks);
-        DVF_LAUNCH_CHECK();
-    } else if (mode == 2) {
-        splitk_reduce_kernel<<<(int)(nb > 4096 ? 4096 : nb), 256, 0, st>>>(ws, out, a.bias, a.KS, total, a.M, HW, a.act,
-                                                                          a.alpha, a.beta);
-        DVF_LAUNCH_CHECK();
-    } else if (mode == 1 && (a.bias || a.act != DVF_ACT_NONE)) {
-        bias_act_kernel<<<(int)(nb > 2048 ? 2048 : nb), 256, 0, st>>>(out, a.bias, a.M, HW, total, a.act, a.alpha, a.beta);
-        DVF_LAUNCH_CHECK();
-    }
-    if (mode == 1 && a.mask)    // atomic accumulation into a zeroed output: the mask pass runs over the finished sums
-        return dvf_act_bwd(out, a.mask, out, nullptr, a.N, a.M, (int)HW, DVF_ACT_RELU, 1.f, 0.f, 1, nullptr, 0, st);
-    return DVF_OK;
+    rc = launch_pipe(a, pl, st);
+    return rc ? rc : finish_output(a, pl.reduce_kpar, ws, io.out, st);
 }
 
 // The packing job of a planned op: w (the layer's stored weights) -> packed (the op's share of the packed buffer).

@@ -14,6 +14,7 @@
     } while (0)
 
 static inline hipStream_t dvf_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // Tuning knobs and ablation switches exist only in a -DDVF_TUNING build (`make TUNING=1`, used by tools/): the product
 // library reads no environment variable on a launch path and carries no code that can switch parts of a kernel off.
