@@ -11,10 +11,11 @@ class PoseExpNet(_PoseExpBase):
         self.output_exp = output_exp
         self._build(6, 6, self.nb_ref_imgs, output_exp)
 
-    def forward(self, imgs):
+    def forward(self, imgs, need_masks=True):
         """``imgs`` is the reference's [B,6,H,W] pair; a (img_a, img_b) tuple of [B,3,H,W] tensors is accepted
-        as well and concatenated virtually inside the first convolution."""
-        masks, pose = self._run(imgs)
+        as well and concatenated virtually inside the first convolution.  ``need_masks=False`` skips the explainability
+        decoder (the masks come back as ``None``) for callers that use the pose alone."""
+        masks, pose = self._run(imgs, need_masks)
         pose = pose.view(pose.size(0), 6)
         if self.training:
             return masks, pose

@@ -33,7 +33,9 @@ class _PoseExpBase(nn.Module):
     def init_weights(self):
         xavier_init_(self)
 
-    def _run(self, frames):
+    def _run(self, frames, need_masks=True):
+        """need_masks=False: the caller discards the masks (the reference's unsupervise.py:95 does), so the explainability
+        decoder -- five upconvs and four heads that no gradient ever reaches -- is not run and the masks are None."""
         outs = []
         h = frames
         for i in range(1, 8):
@@ -41,7 +43,7 @@ class _PoseExpBase(nn.Module):
             outs.append(h)
         pose = SpatialMeanFn.apply(self.pose_pred(h), 0.01)                 # mean(3).mean(2) * 0.01
         masks = [None, None, None, None]
-        if self.output_exp:
+        if self.output_exp and need_masks:
             first = frames[0] if isinstance(frames, (list, tuple)) else frames
             refs = [outs[3], outs[2], outs[1], outs[0], first]
             h = outs[4]
@@ -62,12 +64,12 @@ class PoseExpNet(_PoseExpBase):
         self.output_exp = output_exp
         self._build(3 * (1 + nb_ref_imgs), 6 * nb_ref_imgs, nb_ref_imgs, output_exp)
 
-    def forward(self, target_image, ref_imgs):
+    def forward(self, target_image, ref_imgs, need_masks=True):
         assert(len(ref_imgs) == self.nb_ref_imgs)
         frames = [target_image] + list(ref_imgs)
         if len(frames) > _L.MAX_SEGS:         # the first convolution walks up to 5 frames (nb_ref_imgs <= 4) in place
             raise ValueError(f"nb_ref_imgs = {self.nb_ref_imgs}: at most {_L.MAX_SEGS - 1} reference images are supported")
-        masks, pose = self._run(frames)
+        masks, pose = self._run(frames, need_masks)
         pose = pose.view(pose.size(0), self.nb_ref_imgs, 6)
         if self.training:
             return masks, pose

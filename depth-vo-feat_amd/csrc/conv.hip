@@ -88,6 +88,61 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float *__restrict__ 
     }
 }
 
+// dbias[c] += sum(dy[:, c]) alone (no activation, no dpre to write: the pass behind the weight gradient of a transposed
+// layer).  A pure stream: the block reads its stretch of one (n, c) plane with eight independent 16-byte loads per thread
+// and trip and no bounds test, then at most two trips of four clamped loads.  What bounds it besides the stream is the
+// tail of float atomics: the 16 channels of a 64-byte line of dbias share one memory-side adder, ~15 ns per atomic
+// (1664 blocks of the 16-channel full-resolution layer: 25 us), so the grid is a few hundred blocks (bias_sum_chunks) of up
+// to 1024 threads, which keep as many bytes in flight as four times the blocks of 256 would.
+// part != NULL: the block's sum goes to part[c * nper + n * chunks + chunk] (bias_finish_kernel adds them in index order).
+template <bool VEC>
+__global__ __launch_bounds__(1024) void bias_sum_kernel(const float *__restrict__ dy, float *dbias, int C, int HW, int chunks,
+                                                        float *part, int nper) {
+    __shared__ float red[16];
+    constexpr int U = 8, UT = 4;
+    typedef typename std::conditional<VEC, float __attribute__((ext_vector_type(4))), float>::type V;
+    const int T = blockDim.x;
+    const int plane = blockIdx.x / chunks, chunk = blockIdx.x - plane * chunks;
+    const int c = plane % C;
+    const int E = VEC ? HW >> 2 : HW, per = (E + chunks - 1) / chunks;      // elements (16-byte or 4-byte) of the plane, per block
+    const int beg = chunk * per, n = min(E, beg + per) - beg;
+    const V *p = reinterpret_cast<const V *>(dy + (int64_t)plane * HW) + beg;
+    const V zero = {};
+    V a0 = zero, a1 = zero;
+    int i = threadIdx.x;
+    for (; i + T * (U - 1) < n; i += T * U) {
+        V g[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) g[k] = p[i + T * k];
+#pragma unroll
+        for (int k = 0; k < U; k += 2) { a0 += g[k]; a1 += g[k + 1]; }
+    }
+    for (; i < n; i += T * UT) {                 // (n > 0 here) loads clamped to the last element, masked when added
+        V g[UT];
+#pragma unroll
+        for (int k = 0; k < UT; ++k) g[k] = p[min(i + T * k, n - 1)];
+#pragma unroll
+        for (int k = 0; k < UT; ++k) a0 += (i + T * k < n) ? g[k] : zero;
+    }
+    a0 += a1;
+    float s;
+    if constexpr (VEC) s = (a0[0] + a0[1]) + (a0[2] + a0[3]);
+    else s = a0;
+    s = wave_sum(s);
+    if (T > 64) {
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            s = red[0];
+            for (int w = 1; w < (T >> 6); ++w) s += red[w];
+        }
+    }
+    if (threadIdx.x == 0) {
+        if (part) part[(int64_t)c * nper + (plane / C) * chunks + chunk] = s;
+        else atomicAdd(&dbias[c], s);
+    }
+}
+
 // dbias[c] += part[c][0 .. n) summed in a fixed order (64 strided lane sums, then a fixed tree); one block per channel
 __global__ __launch_bounds__(64) void bias_finish_kernel(const float *__restrict__ part, float *dbias, int n) {
     const float *p = part + (int64_t)blockIdx.x * n;
@@ -584,9 +639,20 @@ static int act_bwd_chunks(int N, int C, int HW, bool has_bias) {
     return chunks;
 }
 
+// Blocks per plane of bias_sum_kernel: planes are split only while the grid is short of one block per CU and a block keeps
+// at least 32 KB; the atomics on one 64-byte line of dbias (16 channels) then number a few hundred at most.
+static int bias_sum_chunks(int N, int C, int HW) {
+    int target = 256;
+    if (const char *t = dvf_tune("DVF_BIAS_BLOCKS")) target = atoi(t);
+    int chunks = 1;
+    while ((int64_t)N * C * chunks * 2 <= target && HW / (chunks * 2) >= 8192) chunks *= 2;
+    return chunks;
+}
+
 int64_t dvf_act_bwd_ws_floats(int N, int C, int HW) {
     if (N <= 0 || C <= 0 || HW <= 0) return DVF_ERR_INVALID_ARG;
-    return (int64_t)C * N * act_bwd_chunks(N, C, HW, true);
+    const int a = act_bwd_chunks(N, C, HW, true), b = bias_sum_chunks(N, C, HW);      // (either pass may run)
+    return (int64_t)C * N * (a > b ? a : b);
 }
 
 int dvf_act_bwd(const float *dy, const float *y, float *dpre, float *dbias, int N, int C, int HW, int act, float alpha,
@@ -597,11 +663,17 @@ int dvf_act_bwd(const float *dy, const float *y, float *dpre, float *dbias, int 
     if (dbias && !accumulate_dbias && hipMemsetAsync(dbias, 0, sizeof(float) * C, st) != hipSuccess) return DVF_ERR_LAUNCH;
     const bool vec = (HW % 4 == 0) && ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(y) |
                                         reinterpret_cast<uintptr_t>(dpre)) % 16 == 0);
-    const int chunks = act_bwd_chunks(N, C, HW, dbias != nullptr);
+    const bool sums_only = !dpre && act == DVF_ACT_NONE;
+    const int chunks = sums_only ? bias_sum_chunks(N, C, HW) : act_bwd_chunks(N, C, HW, dbias != nullptr);
     const int64_t planes = (int64_t)N * C;
     // with the scratch: per-block partial sums, added in index order by bias_finish_kernel (else float atomics on dbias)
     float *part = (dbias && ws && ws_floats >= dvf_act_bwd_ws_floats(N, C, HW)) ? ws : nullptr;
-    if (vec) act_bwd_kernel<true><<<(unsigned)(planes * chunks), 256, 0, st>>>(dy, y, dpre, dbias, C, HW, act, alpha, beta, chunks, part, N * chunks);
+    if (sums_only) {
+        const int per = ((vec ? HW >> 2 : HW) + chunks - 1) / chunks;          // loads per block
+        const int threads = per <= 256 ? 64 : per <= 8192 ? 256 : 1024;
+        if (vec) bias_sum_kernel<true><<<(unsigned)(planes * chunks), threads, 0, st>>>(dy, dbias, C, HW, chunks, part, N * chunks);
+        else bias_sum_kernel<false><<<(unsigned)(planes * chunks), threads, 0, st>>>(dy, dbias, C, HW, chunks, part, N * chunks);
+    } else if (vec) act_bwd_kernel<true><<<(unsigned)(planes * chunks), 256, 0, st>>>(dy, y, dpre, dbias, C, HW, act, alpha, beta, chunks, part, N * chunks);
     else act_bwd_kernel<false><<<(unsigned)(planes * chunks), 256, 0, st>>>(dy, y, dpre, dbias, C, HW, act, alpha, beta, chunks, part, N * chunks);
     DVF_LAUNCH_CHECK();
     if (part) {

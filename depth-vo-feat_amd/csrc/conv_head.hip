@@ -1,7 +1,8 @@
 // Direct (non-MFMA) kernels for the 1-4 channel 3x3 prediction heads (predict_disp*, DispNetS.py:66-69; the
 // explainability-mask heads, PoseExpNet_sfm.py:43-46).  A 32-row MFMA tile would be 88-97 % padding for these
 // layers; they are memory-bound (read the C_in-channel activation once), so plain FMAs over an LDS-staged tile are
-// the right tool: forward, dgrad and wgrad.  3x3, stride 1, padding 1, single input segment, C_out <= 4.
+// the right tool for forward and dgrad; the weight gradient streams both operands through registers.  3x3, stride 1,
+// padding 1, single input segment, C_out <= 4.
 #include "conv_head.h"
 #include "conv_epilogue.h"
 
@@ -12,7 +13,6 @@ using dvfp::apply_act;
 constexpr int HT_W = 64, HT_H = 4;          // pixel tile per block (256 threads, one pixel each)
 constexpr int HP_W = HT_W + 2, HP_H = HT_H + 2;
 constexpr int HCK = 8;                      // input channels staged per pass (forward)
-constexpr int HWK = 7;                      // ... in wgrad: 7 channels x 9 taps = 63 columns, one per lane
 
 // stage `nch` channel planes (tile + halo 1, zero outside the image) into lds[ch][HP_H][HP_W]
 __device__ __forceinline__ void stage_tile(float *lds, const float *__restrict__ src, int64_t plane, int nch, int H, int W,
@@ -252,58 +252,126 @@ __global__ __launch_bounds__(256) void head_dgrad_kernel(const float *__restrict
 }
 
 // dW[mo][c][ta][tb] (+)= sum_{n,y,x} dpre[n][mo][y][x] * in[n][c][y+ta-1][x+tb-1]
-// grid (channel chunks of HWK, pixel-tile groups); thread t < nch*9 owns column (c, tap) and walks the tile's pixels
+// Streaming form: both operands go from memory to registers once (16-byte lanes when VEC), nothing is staged in LDS.
+// A thread owns one unit = 4 pixels of a row x RS rows of one image and CCH input channels, and keeps the
+// 9 x CCH x MO sums of its pixels in registers.  It walks the RS + 2 input rows of its unit top-down: input row r meets
+// the dpre rows r+1, r, r-1 (kernel rows 0, 1, 2), which are held as a three-row window, so a step costs CCH row loads
+// (4 pixels + the two neighbours) and one dpre row load for 36 x CCH x MO FMAs; the loads of the next step are issued
+// before the FMAs of the current one.  Units are numbered (image, row segment, 4-pixel group) and handed to lanes in that
+// order, so every lane of a wave is busy whatever the width.  grid (channel chunks of CCH, unit-block groups).
+// The sums are combined by wave reduction, then across the four waves: one atomic (or one part[] entry) per block and output.
 // part != NULL: the block's sums go to part[blockIdx.y][m][c][tap] (head_wgrad_finish_kernel adds the groups in order)
-template <int MO>
+template <bool VEC>
+__device__ __forceinline__ void hw_load4(const float *__restrict__ p, int x0, int W, bool ok, float (&v)[4]) {
+    if (VEC) {
+        typedef float f4 __attribute__((ext_vector_type(4)));
+        f4 t = {0.f, 0.f, 0.f, 0.f};
+        if (ok) t = *reinterpret_cast<const f4 *>(p);              // (W % 4 == 0: the whole group is inside the row)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = t[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = (ok && x0 + j < W) ? p[j] : 0.f;
+    }
+}
+
+template <int MO, int CCH, bool VEC>
 __global__ __launch_bounds__(256) void head_wgrad_kernel(const float *__restrict__ in, const float *__restrict__ dpre,
-                                                         float *dw, int N, int C, int H, int W, int tilesX, int tilesY,
-                                                         float *part = nullptr) {
-    __shared__ float tin[HWK * HP_H * HP_W];
-    __shared__ float tdp[MO * HT_H * HT_W];
-    __shared__ float red[4 * HWK * 9 * MO];
-    const int c0 = blockIdx.x * HWK, nch = min(HWK, C - c0);
+                                                         float *dw, int C, int H, int W, int RS, int xgroups, int segs,
+                                                         int64_t units, float *part = nullptr) {
+    constexpr int A = CCH * 9 * MO;
+    __shared__ float red[4 * A];
+    const int c0 = blockIdx.x * CCH;
     const int64_t plane = (int64_t)H * W;
-    // 4 waves split the tile's rows; lane < nch*9 owns one (c, tap) column
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int col_c = lane / 9, col_t = lane - col_c * 9, ta = col_t / 3, tb = col_t - ta * 3;
-    const bool active = lane < nch * 9;
-    float acc[MO];
+    const int upi = segs * xgroups;                                // units per image
+    float acc[CCH][9][MO];
 #pragma unroll
-    for (int m = 0; m < MO; ++m) acc[m] = 0.f;
-    const int ntiles = N * tilesX * tilesY;
-    for (int tile = blockIdx.y; tile < ntiles; tile += gridDim.y) {
-        const int n = tile / (tilesX * tilesY), r = tile - n * (tilesX * tilesY), tY = r / tilesX, tX = r - tY * tilesX;
-        const int y0 = tY * HT_H, x0 = tX * HT_W;
-        __syncthreads();
-        stage_tile(tin, in + ((int64_t)n * C + c0) * plane, plane, nch, H, W, y0, x0);
-        for (int e = threadIdx.x; e < MO * HT_H * HT_W; e += 256) {
-            const int m = e / (HT_H * HT_W), q = e - m * (HT_H * HT_W), py = q / HT_W, px = q - py * HT_W;
-            const int y = y0 + py, x = x0 + px;
-            tdp[e] = (y < H && x < W) ? dpre[((int64_t)n * MO + m) * plane + (int64_t)y * W + x] : 0.f;
-        }
-        __syncthreads();
-        if (active) {
-            const float *src = tin + col_c * (HP_H * HP_W) + (wave + ta) * HP_W + tb;      // row `wave` of the tile
-            const float *dp = tdp + wave * HT_W;
-#pragma unroll 8
-            for (int px = 0; px < HT_W; ++px) {
-                const float v = src[px];
+    for (int c = 0; c < CCH; ++c)
 #pragma unroll
-                for (int m = 0; m < MO; ++m) acc[m] = fmaf(dp[m * (HT_H * HT_W) + px], v, acc[m]);     // broadcast reads
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int m = 0; m < MO; ++m) acc[c][t][m] = 0.f;
+    for (int64_t ub = blockIdx.y; ub * 256 < units; ub += gridDim.y) {
+        const int64_t u = ub * 256 + threadIdx.x;
+        const bool live = u < units;
+        const int n = live ? (int)(u / upi) : 0, q = live ? (int)(u - (int64_t)n * upi) : 0;
+        const int seg = q / xgroups, xg = q - seg * xgroups;
+        const int y0 = seg * RS, y1 = min(H, y0 + RS), x0 = xg * 4;
+        const float *ip = in + ((int64_t)n * C + c0) * plane + x0;
+        const float *dp = dpre + (int64_t)n * MO * plane + x0;
+        const bool lok = x0 > 0, rok = x0 + 4 < W;
+        // input row r of the CCH channels: columns x0-1 .. x0+4 (zero outside the image, for a channel >= C, for a dead lane)
+        auto load_in = [&](int r, float (&x)[CCH][6]) __attribute__((always_inline)) {
+            const bool ok = live && r >= 0 && r < H;
+            const int64_t ro = (int64_t)r * W;
+#pragma unroll
+            for (int c = 0; c < CCH; ++c) {
+                const bool okc = ok && c0 + c < C;
+                const float *p = ip + c * plane + ro;
+                float v[4];
+                hw_load4<VEC>(p, x0, W, okc, v);
+                x[c][0] = (okc && lok) ? p[-1] : 0.f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) x[c][1 + j] = v[j];
+                x[c][5] = (okc && rok) ? p[4] : 0.f;
             }
+        };
+        // dpre row y of this unit (zero outside its own rows y0 .. y1-1: the neighbouring unit sums those)
+        auto load_dp = [&](int y, float (&g)[MO][4]) __attribute__((always_inline)) {
+            const bool ok = live && y >= y0 && y < y1;
+#pragma unroll
+            for (int m = 0; m < MO; ++m) hw_load4<VEC>(dp + m * plane + (int64_t)y * W, x0, W, ok, g[m]);
+        };
+        float d[3][MO][4], dn[MO][4], xc[CCH][6], xn[CCH][6];     // d: dpre rows r-1, r, r+1
+#pragma unroll
+        for (int m = 0; m < MO; ++m)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) d[0][m][j] = d[1][m][j] = 0.f;
+        load_dp(y0, d[2]);
+        load_in(y0 - 1, xc);
+        for (int i = 0; i < RS + 2; ++i) {
+            const int r = y0 - 1 + i;
+            load_in(i + 1 < RS + 2 ? r + 1 : H, xn);              // (past the last step: row H reads as zero, no load)
+            load_dp(r + 2, dn);
+#pragma unroll
+            for (int c = 0; c < CCH; ++c)
+#pragma unroll
+                for (int ta = 0; ta < 3; ++ta)
+#pragma unroll
+                    for (int tb = 0; tb < 3; ++tb)
+#pragma unroll
+                        for (int m = 0; m < MO; ++m)
+#pragma unroll
+                            for (int j = 0; j < 4; ++j)
+                                acc[c][ta * 3 + tb][m] = fmaf(d[2 - ta][m][j], xc[c][j + tb], acc[c][ta * 3 + tb][m]);
+#pragma unroll
+            for (int m = 0; m < MO; ++m)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { d[0][m][j] = d[1][m][j]; d[1][m][j] = d[2][m][j]; d[2][m][j] = dn[m][j]; }
+#pragma unroll
+            for (int c = 0; c < CCH; ++c)
+#pragma unroll
+                for (int j = 0; j < 6; ++j) xc[c][j] = xn[c][j];
         }
     }
-    // combine the 4 waves, one atomic per output
-    if (active)
+    // wave sums, then the four waves in a fixed order: thread a < A owns output a = (c * 9 + tap) * MO + m
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
-        for (int m = 0; m < MO; ++m) red[(wave * MO + m) * (HWK * 9) + lane] = acc[m];
+    for (int c = 0; c < CCH; ++c)
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int m = 0; m < MO; ++m) {
+                const float s = wave_sum(acc[c][t][m]);
+                if (lane == 0) red[wave * A + (c * 9 + t) * MO + m] = s;
+            }
     __syncthreads();
-    if (wave == 0 && active) {
-#pragma unroll
-        for (int m = 0; m < MO; ++m) {
-            const float s = (red[(0 * MO + m) * (HWK * 9) + lane] + red[(1 * MO + m) * (HWK * 9) + lane]) +
-                            (red[(2 * MO + m) * (HWK * 9) + lane] + red[(3 * MO + m) * (HWK * 9) + lane]);
-            const int64_t o = ((int64_t)m * C + c0 + col_c) * 9 + col_t;
+    const int a = threadIdx.x;
+    if (a < A) {
+        const int c = a / (9 * MO), q = a - c * (9 * MO), t = q / MO, m = q - t * MO;
+        if (c0 + c < C) {
+            const float s = (red[a] + red[A + a]) + (red[2 * A + a] + red[3 * A + a]);
+            const int64_t o = ((int64_t)m * C + c0 + c) * 9 + t;
             if (part) part[(int64_t)blockIdx.y * MO * C * 9 + o] = s;
             else atomicAdd(&dw[o], s);
         }
@@ -419,7 +487,7 @@ bool dvf_head_applicable(const dvf_conv_desc *d, int nseg) {
 // few dozen blocks) lose to conv_pipe_kernel even with 94-97 % of its MFMA rows padding:
 //   forward 128->2 @32x104   46 us direct            dgrad 128->1 @32x104   48 us direct, 18 us conv_pipe
 //                                                    dgrad  64->1 @64x208   28 us direct, 18 us conv_pipe
-// The weight gradient stays direct at every size (13-58 us against 22-73 us).
+// The weight gradient stays direct at every size (round 3: 13-58 us against 22-73 us; the streaming kernel: 9-23 us).
 bool dvf_head_fwd_applicable(const dvf_conv_desc *d, int nseg) {
     static const int maxc = dvf_tune("DVF_HEAD_FWD_MAXC") ? atoi(dvf_tune("DVF_HEAD_FWD_MAXC")) : 127;      // tuning knob
     return dvf_head_applicable(d, nseg) && d->C_in <= maxc;
@@ -541,35 +609,56 @@ int dvf_head_dgrad(const dvf_conv_desc *d, const float *dpre, const float *w, fl
     return DVF_OK;
 }
 
-static void head_wgrad_grid(const dvf_conv_desc *d, int &tilesX, int &tilesY, int &chunks, int &groups) {
-    tilesX = cdiv(d->W_in, HT_W); tilesY = cdiv(d->H_in, HT_H);
-    chunks = cdiv(d->C_in, HWK);
-    const int ntiles = d->N * tilesX * tilesY;
-    groups = 2048 / chunks;
+// Launch shape of head_wgrad_kernel, a function of the layer geometry alone (the scratch size follows from it): CCH input
+// channels per thread (4 where that still gives two blocks per CU, else 2; the 3-4 channel heads always 2: 9 * CCH * MO
+// accumulators), RS rows per unit (8, halved down to 2 while the grid is short of ~1.6 blocks per CU: every unit re-reads
+// two halo rows, from cache, so short units cost loads and long ones parallelism), and at most ~1024 blocks, so that one
+// output sees at most 1024 / chunks float atomics.
+struct HeadWgradGrid { int cch, RS, xgroups, segs, chunks, groups; int64_t units; };
+static HeadWgradGrid head_wgrad_grid(const dvf_conv_desc *d) {
+    HeadWgradGrid g;
+    g.xgroups = cdiv(d->W_in, 4);
+    auto blocks = [&](int cch, int rs) {
+        return (int64_t)cdiv(d->C_in, cch) * (((int64_t)d->N * cdiv(d->H_in, rs) * g.xgroups + 255) / 256);
+    };
+    const int min_blocks = 400, max_blocks = 1024;
+    g.cch = (d->C_out <= 2 && blocks(4, 8) >= 512) ? 4 : 2;
+    g.RS = 8;
+    if (const char *t = dvf_tune("DVF_HEAD_WG_CCH")) g.cch = (atoi(t) == 4 && d->C_out <= 2) ? 4 : 2;
+    while (g.RS > 2 && blocks(g.cch, g.RS) < min_blocks) g.RS >>= 1;
+    if (const char *t = dvf_tune("DVF_HEAD_WG_RS")) g.RS = atoi(t) > 0 ? atoi(t) : g.RS;
+    g.segs = cdiv(d->H_in, g.RS);
+    g.units = (int64_t)d->N * g.segs * g.xgroups;
+    g.chunks = cdiv(d->C_in, g.cch);
+    const int64_t nub = (g.units + 255) / 256;
+    int64_t groups = max_blocks / g.chunks;
     if (groups < 1) groups = 1;
-    if (groups > ntiles) groups = ntiles;
+    if (groups > nub) groups = nub;
+    g.groups = (int)groups;
+    return g;
 }
 
 int64_t dvf_head_wgrad_ws_floats(const dvf_conv_desc *d) {
-    int tilesX, tilesY, chunks, groups;
-    head_wgrad_grid(d, tilesX, tilesY, chunks, groups);
-    return (int64_t)groups * d->C_out * d->C_in * 9;
+    return (int64_t)head_wgrad_grid(d).groups * d->C_out * d->C_in * 9;
 }
 
 int dvf_head_wgrad(const dvf_conv_desc *d, const float *in, const float *dpre, float *dw, int accumulate, hipStream_t st,
                    float *ws, int64_t ws_floats) {
     if (!accumulate && hipMemsetAsync(dw, 0, sizeof(float) * (size_t)d->C_out * d->C_in * 9, st) != hipSuccess)
         return DVF_ERR_LAUNCH;
-    int tilesX, tilesY, chunks, groups;
-    head_wgrad_grid(d, tilesX, tilesY, chunks, groups);
-    const dim3 grid(chunks, groups);
+    const HeadWgradGrid g = head_wgrad_grid(d);
+    const dim3 grid(g.chunks, g.groups);
     float *part = (ws && ws_floats >= dvf_head_wgrad_ws_floats(d)) ? ws : nullptr;
-    HEAD_DISPATCH(d->C_out, (head_wgrad_kernel<MO><<<grid, 256, 0, st>>>(in, dpre, dw, d->N, d->C_in, d->H_in, d->W_in, tilesX,
-                                                                        tilesY, part)));
+    const bool vec = d->W_in % 4 == 0 && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(dpre)) & 15) == 0;
+#define HEAD_WGRAD_GO(CCH, VEC) head_wgrad_kernel<MO, CCH, VEC><<<grid, 256, 0, st>>>(in, dpre, dw, d->C_in, d->H_in, d->W_in, g.RS, g.xgroups, g.segs, g.units, part)
+    HEAD_DISPATCH(d->C_out, {
+        if (MO <= 2 && g.cch == 4) { if (vec) HEAD_WGRAD_GO((MO <= 2 ? 4 : 2), true); else HEAD_WGRAD_GO((MO <= 2 ? 4 : 2), false); }
+        else { if (vec) HEAD_WGRAD_GO(2, true); else HEAD_WGRAD_GO(2, false); } });
+#undef HEAD_WGRAD_GO
     DVF_LAUNCH_CHECK();
     if (part) {
         const int n = d->C_out * d->C_in * 9;
-        head_wgrad_finish_kernel<<<(n + 255) / 256, 256, 0, st>>>(part, dw, n, groups);
+        head_wgrad_finish_kernel<<<(n + 255) / 256, 256, 0, st>>>(part, dw, n, g.groups);
         DVF_LAUNCH_CHECK();
     }
     dvf_plan_note(DVF_K_HEAD_WGRAD, d->C_out, part ? 1 : 0);

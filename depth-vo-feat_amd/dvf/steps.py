@@ -49,6 +49,15 @@ def _side_by_side(aux_fn, main_fn):
     return a_out, m_out
 
 
+def _pose_only(pose_net, frames):
+    """pose_net(frames) for a body that discards the explainability masks: a PoseExpNet is told not to compute them (its
+    decoder is a third of the network's forward time and no gradient reaches it); any other module is called as it is."""
+    from PoseExpNet_sfm import _PoseExpBase
+    if isinstance(getattr(pose_net, "module", pose_net), _PoseExpBase):
+        return pose_net(frames, need_masks=False)
+    return pose_net(frames)
+
+
 def _identity_share(counts, n_views):
     """Share of the pixels won by an identity candidate, from the selection counts of MinReprojLossFn (a handful of
     integers: no image-sized kernel)."""
@@ -67,7 +76,7 @@ def unsupervise_losses(depth_net, pose_net, batch, feat_extractor=None, img_scal
     counts = []
     R2, R1, L2 = batch["img_R2"], batch["img_R1"], batch["img_L2"]
     # unsupervise.py:92,95 (cat(R2, R1) done virtually) and :94 (intended: finest disparity)
-    (_, T_2to1), disps = _side_by_side(lambda: pose_net((R2, R1)), lambda: depth_net(R2))
+    (_, T_2to1), disps = _side_by_side(lambda: _pose_only(pose_net, (R2, R1)), lambda: depth_net(R2))
     inv_depth = disps[0]
     depth = reciprocal(inv_depth, depth_eps).squeeze(1)            # :99
     img_loss = LF.photometric_reconstruction_loss(R2, R1, L2, depth, T_2to1, batch["T_R2L"], batch["K"], batch["Kinv"],
@@ -179,7 +188,7 @@ def unsupervise_dvo_losses(depth_net, pose_net, batch, img_scale=0.004, smooth_w
     unsupervise_losses."""
     from dvf.ops import PhotoLossFn
     R2, R1, L2 = batch["img_R2"], batch["img_R1"], batch["img_L2"]
-    (_, T_2to1), disps = _side_by_side(lambda: pose_net((R2, R1)), lambda: depth_net(R2))
+    (_, T_2to1), disps = _side_by_side(lambda: _pose_only(pose_net, (R2, R1)), lambda: depth_net(R2))
     inv_depth = disps[0]
     depth = reciprocal(inv_depth, depth_eps)                               # [B,1,H,W]
     pose = torch.stack((batch["T_R2L"], T_2to1), dim=0)                    # [V=2,B,6]: view 0 = left image, view 1 = R1
@@ -199,7 +208,7 @@ def paper_losses(depth_net, pose_net, batch, feat_extractor=None, img_scale=0.00
     feature maps.  batch["T_R2L_se3"] is the stereo pose as the dataset holds it."""
     import loss_functions_caffe as LC
     R2, R1, L2 = batch["img_R2"], batch["img_R1"], batch["img_L2"]
-    (_, T_2to1), disps = _side_by_side(lambda: pose_net((R2, R1)), lambda: depth_net(R2))
+    (_, T_2to1), disps = _side_by_side(lambda: _pose_only(pose_net, (R2, R1)), lambda: depth_net(R2))
     inv_depth = disps[0]
     depth = reciprocal(inv_depth, depth_eps)                               # depth = (inv_depth + 1e-4)^-1  (:4355-4367)
     poses = (batch["T_R2L_se3"], T_2to1)
