@@ -9,8 +9,18 @@ import time
 import torch
 import torch.distributed as dist
 
+from . import augment
 from .engine import FlatAdam, GraphedStep
 from .synthetic import synthetic_batch
+
+
+def _augment_ops(text):
+    """argparse type of --augment: a comma list of op names -> tuple of ops."""
+    import argparse
+    try:
+        return augment.parse_ops(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
 
 
 def add_common_flags(parser):
@@ -58,6 +68,15 @@ def add_common_flags(parser):
                    help="feed the dataset's T_R2L file vector (0,0,0,Tx,0,0) unchanged into pose_vec2mat / the stereo-pose "
                         "MSE target, exactly as the reference does (unsupervise.py:101, train.py:201); default: convert it "
                         "to the (t, r-euler) order those functions read (un_dataset.to_batch)")
+    g.add_argument("--augment", nargs="?", type=_augment_ops, const=augment.OPS, default=None, metavar="OPS",
+                   help="training augmentation on the GPU, one draw per sample applied to all its frames (seeded by --seed and the "
+                        "rank); OPS is a comma list out of flip,zoom,colour (no value: all three).  flip: horizontal mirror "
+                        "with probability 0.5, the stereo baseline changes sign; zoom: zoom by U[1, 1.15] per axis to an integer "
+                        "size, then a random crop back to the input size (bilinear); colour: with probability 0.5 gamma "
+                        "U[0.8, 1.2], brightness U[0.5, 2.0] and per-channel gains U[0.8, 1.2].  An extension in place of the "
+                        "reference's custom_transforms.py (parity unpinned, tests/augment_ref.py is the definition), with two "
+                        "departures: the intrinsics follow the exact pixel map (integer zoomed size, half-pixel term) instead "
+                        "of the untruncated factor, and a flip mirrors cx as W - 1 - cx instead of w - cx")
 
 
 def ssim_kwargs(args):
@@ -166,14 +185,31 @@ def run_training(args, nets, loss_fn, lr, betas, weight_decay, term_names, ckpt_
                     yield un_dataset.to_batch(sample, device, getattr(args, "reference_stereo_pose", False))
         feed = feed()
     KEYS = ("img_R2", "img_R1", "img_L2", "K", "Kinv", "T_R2L", "T_R2L_se3")
+    aug_ops = getattr(args, "augment", None)
+    if aug_ops is not None:
+        aug_gen = torch.Generator().manual_seed(977 * args.seed + rank + 31)
+        pristine = None if feed is not None else \
+            {k: ([t.clone() for t in v] if isinstance(v, list) else v.clone()) for k, v in batch.items()}
+
+        def next_records():
+            rec = augment.sample_params(aug_gen, args.batch_size, args.height, args.width, aug_ops)
+            augment.validate_params(rec, args.height, args.width)
+            # a fresh pinned tensor per step: a staging buffer whose copy may still be in flight is never rewritten
+            return rec.pin_memory().to(device, non_blocking=True)
 
     def load_next():
         nxt = next(feed)
+        if aug_ops is not None:
+            # loader tensor -> static tensor in one pass, in place of the copies below
+            augment.augment_batch({k: nxt[k].reshape(batch[k].shape) for k in KEYS}, batch, next_records())
+            return
         for k in KEYS:
             batch[k].copy_(nxt[k].reshape(batch[k].shape), non_blocking=True)
 
     if feed is not None:
         load_next()              # the warm-up / capture steps below already train: they must see real data, not noise
+    elif aug_ops is not None:
+        augment.augment_batch(pristine, batch, next_records())
     acc = torch.zeros(len(term_names), device=device)            # device-side running sums: no per-step .item()
 
     def step():
@@ -195,6 +231,8 @@ def run_training(args, nets, loss_fn, lr, betas, weight_decay, term_names, ckpt_
         for it in range(args.steps_per_epoch):
             if feed is not None and (epoch, it) != (0, 0):
                 load_next()
+            elif feed is None and aug_ops is not None:
+                augment.augment_batch(pristine, batch, next_records())    # a new view of the synthetic batch every step
             runner()
             if getattr(args, "log_interval", 0) and rank == 0 and (it + 1) % args.log_interval == 0:
                 # (one host sync per log interval; the reference syncs on five .item() calls every step, train.py:205-209)

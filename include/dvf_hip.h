@@ -151,6 +151,31 @@ int dvf_imresize_u8(const uint8_t *src_hwc, int IH, int IW, int C, const int *hb
                     const int *vbounds, const int *vcoef, int vksize, uint8_t *tmp, int *minmax, float *dst_chw, int OH, int OW,
                     void *stream);
 
+/* ---------------------------------------------------------------- training augmentation (build-side extension, opt-in)
+ * Random horizontal flip, zoom-and-crop and colour perturbation on the device, in place of the host transforms of
+ * pytorch_version/custom_transforms.py:46-84 (wired in train.py:89-101).  tests/augment_ref.py is the definition; parity is
+ * unpinned (the reference's transforms no longer import) and departs from them in two documented places (below).
+ * params [B,12], one record per sample, applied to every frame of the sample:
+ *   {flip 0|1, sw, sh, ox, oy, colour_on 0|1, gamma, brightness, gain_r, gain_g, gain_b, 0}: the frame is zoomed to sw x sh
+ *   (integers >= W, H), cropped at the integer offset (ox, oy), then mirrored.  The caller validates the records
+ *   (dvf/augment.py::validate_params); tap indices are clamped, so no record makes the kernel read outside a frame.
+ * dvf_augment_frames: src / dst are HOST arrays of F device pointers (1 <= F <= 8), each [B,3,H,W]; one launch for all frames.
+ *   For output (y, x): xc = flip ? W-1-x : x; u = (xc + ox + 0.5) W/sw - 0.5, v = (y + oy + 0.5) H/sh - 0.5, clamped to the
+ *   frame; bilinear taps x0 = floor(u), x1 = min(x0+1, W-1) (likewise y).  sw = W, ox = 0 gives a bit-exact copy / mirror.
+ *   Colour (only where colour_on; otherwise bits pass through): n = value/value_max; n = n^gamma, evaluated as
+ *   exp2(gamma log2 n); value = value_max clamp(n brightness gain_c, 0, 1).
+ *   The gather reads the whole source: a dst that overlaps any src or another dst is DVF_ERR_INVALID_ARG, as is C != 3.
+ * dvf_augment_geometry: K' = A K M, Kinv' = M Kinv A^-1 [B,3,3] with sx = sw/W, sy = sh/H, cxo = (sx-1)/2 - ox, cyo likewise,
+ *   A = [[sx,0,cxo],[0,sy,cyo],[0,0,1]], M = I, or under flip A = [[-sx,0,W-1-cxo],[0,sy,cyo],[0,0,1]], M = diag(-1,1,1) --
+ *   the exact map of pixel indices in the warp's convention (integer index = pixel centre, inverse_warp.py:8-15); the
+ *   reference scales by the untruncated factor without the half-pixel term (custom_transforms.py:73-74,81-82) and mirrors
+ *   cx as w - cx (:55).  Under flip T_tr [B,6] (t, r) is multiplied by (-1,1,1,1,-1,-1) and T_se3 [B,6] (w, u) by
+ *   (1,-1,-1,-1,1,1).  Every output may alias its input. */
+int dvf_augment_frames(const float *const *src, float *const *dst, int F, const float *params, int B, int C, int H, int W,
+                       float value_max, void *stream);
+int dvf_augment_geometry(const float *params, const float *K, const float *Kinv, const float *T_tr, const float *T_se3,
+                         float *K_out, float *Kinv_out, float *T_tr_out, float *T_se3_out, int B, int W, int H, void *stream);
+
 /* ---------------------------------------------------------------- edge-aware smoothness (paper / Caffe graph variant)
  * experiments/depth_odometry_feature/train.prototxt:4452-4661 with caffe/include/caffe/filler.hpp:267-316 and
  * abs_loss_layer.cu:10-34: loss_out[0] (+)= weight * (sum |exp(-k sum_c |d_y I_c|) d_y D| + sum |exp(-k sum_c |d_x I_c|) d_x D|) / B
