@@ -77,3 +77,59 @@ class pose_framework_KITTI(data.Dataset):
 
     def __len__(self):
         return len(self.samples)
+
+
+class DepthValidationSet(data.Dataset):
+    """Frames with ground-truth depth for ``dvf.cli.validate_depth``.  Layout: ``root/val.txt`` holds one stem per line,
+    ``root/image/<stem>.png|jpg`` the frame and ``root/depth/<stem>.npy`` a float32 [Hg,Wg] map in metres with 0 for no
+    measurement (a projected LiDAR sweep).  A sample is (frame [3,img_height,img_width] float32, depth [Hg,Wg] float32): the
+    frame goes through the same ``imread`` / ``imresize`` and keeps the value range (0..255) that ``un_dataset.dataset``
+    hands to ``un_dataset.to_batch``; the depth keeps its own size -- the prediction is brought to it, not the other way.
+    ``shapes`` lists every sample's (Hg, Wg), read once from the .npy headers (``mmap_mode='r'``: no map is loaded)."""
+
+    def __init__(self, root, img_height, img_width):
+        self.root, self.height, self.width = root, img_height, img_width
+        with open(os.path.join(root, "val.txt")) as f:
+            self.stems = [line.strip() for line in f if line.strip()]
+        self.images = []
+        for stem in self.stems:
+            found = [p for p in (os.path.join(root, "image", stem + ext) for ext in (".png", ".jpg")) if os.path.exists(p)]
+            if not found:
+                raise FileNotFoundError(f"no image/{stem}.png or .jpg under {root}")
+            self.images.append(found[0])
+        self.depths = [os.path.join(root, "depth", stem + ".npy") for stem in self.stems]
+        self.shapes = []
+        for p in self.depths:
+            shape = tuple(np.load(p, mmap_mode="r", allow_pickle=False).shape)
+            if len(shape) != 2:
+                raise ValueError(f"{p}: expected a [H,W] depth map, got shape {shape}")
+            self.shapes.append(shape)
+
+    def __getitem__(self, index):
+        img = imresize(imread(self.images[index]).astype(np.float32), (self.height, self.width)).astype(np.float32)
+        depth = np.load(self.depths[index], allow_pickle=False).astype(np.float32)
+        return (torch.from_numpy(np.ascontiguousarray(np.transpose(img, (2, 0, 1)))),
+                torch.from_numpy(np.ascontiguousarray(depth)))
+
+    def __len__(self):
+        return len(self.stems)
+
+    def batches(self, batch_size):
+        """Index lists for a DataLoader's ``batch_sampler``: consecutive samples of equal ground-truth size, at most
+        ``batch_size`` of them, so that a batch's depth maps stack into one [B,Hg,Wg] tensor."""
+        out = []
+        for i, shape in enumerate(self.shapes):
+            if out and len(out[-1]) < batch_size and self.shapes[out[-1][-1]] == shape:
+                out[-1].append(i)
+            else:
+                out.append([i])
+        return out
+
+    def loader(self, batch_size, num_workers=0):
+        return data.DataLoader(self, batch_sampler=self.batches(batch_size), num_workers=num_workers)
+
+
+def depth_validation_set(root, img_height, img_width):
+    """The depth validation set under ``root`` (see ``DepthValidationSet``); ``.loader(batch_size)`` batches it by
+    ground-truth size."""
+    return DepthValidationSet(root, img_height, img_width)

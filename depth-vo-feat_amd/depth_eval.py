@@ -4,7 +4,13 @@
 and predicted depths of the valid pixels it returns (abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3).  The reference module
 imports cv2 (absent in the build image), so it cannot be imported for vectors: parity is pinned by hand-computed known
 answers in tests/test_depth_eval.py.  ``evaluate`` applies the usual KITTI protocol of tools/eval_depth.py around it:
-depth cap, optional Garg crop, optional median scaling."""
+depth cap, optional Garg crop, optional median scaling.
+
+Run as a script (``python depth_eval.py --pretrained-disp CKPT --val-depth-root DIR``) it evaluates a checkpoint on the GPU
+through dvf.cli.validate_depth / dvf.metrics.depth_metrics instead.  The two differ in one documented place: ``evaluate``
+uses numpy's median, the MEAN OF THE TWO middle elements for an even count, while the device path takes torch.median's lower
+median as the reference's training-side compute_errors does (loss_functions_sfm.py:104); the mean-of-two form is not
+reproduced on the device.  The device path also clamps once, before scaling, unless asked to reclamp."""
 import numpy as np
 
 
@@ -40,3 +46,38 @@ def evaluate(gt_depths, pred_depths, min_depth=1e-3, max_depth=80.0, garg_crop=T
             p = np.clip(p, min_depth, max_depth)
         rows.append(compute_errors(g, p))
     return tuple(np.mean(np.array(rows), axis=0))
+
+
+def main(argv=None):
+    """Evaluate a depth checkpoint against a depth validation tree on the GPU and print the seven Eigen metrics plus
+    abs_diff (the line train.py --val-depth-root prints after every epoch)."""
+    import argparse
+    import torch
+    from DispNetS import DispNetS
+    from dataset import depth_validation_set
+    from dvf import cli
+    parser = argparse.ArgumentParser(description="Depth evaluation against ground truth on MI355X",
+                                     formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("--pretrained-disp", required=True, metavar="PATH", help="DispNetS checkpoint (best_depth_checkpoint.pth.tar)")
+    parser.add_argument("--val-depth-root", required=True, metavar="DIR",
+                        help="val.txt, image/<stem>.png|jpg, depth/<stem>.npy in metres (0 = no measurement)")
+    parser.add_argument("--height", type=int, default=256)
+    parser.add_argument("--width", type=int, default=832)
+    parser.add_argument("-b", "--batch-size", type=int, default=4)
+    parser.add_argument("--no-crop", action="store_true", help="all pixels instead of the Garg crop")
+    parser.add_argument("--no-median-scaling", action="store_true", help="compare the prediction as it is")
+    args = parser.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("this build runs on MI355X only: no CUDA/HIP device visible and there is no CPU fallback")
+    device = torch.device("cuda", 0)
+    net = DispNetS()
+    cli.load_pretrained(net, args.pretrained_disp)
+    net.to(device)
+    loader = depth_validation_set(args.val_depth_root, args.height, args.width).loader(args.batch_size)
+    metrics = cli.validate_depth(net, loader, device, crop=not args.no_crop, median_scaling=not args.no_median_scaling)
+    print(cli.format_depth_metrics(metrics), flush=True)
+    return metrics
+
+
+if __name__ == "__main__":
+    main()

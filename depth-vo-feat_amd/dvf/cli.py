@@ -158,8 +158,51 @@ def validate(pose_net, val_loader, device):
     return float(total) / max(len(val_loader.dataset), 1)
 
 
-def run_training(args, nets, loss_fn, lr, betas, weight_decay, term_names, ckpt_names, n_views=2, val_fn=None):
-    """Epoch loop.  ``loss_fn(batch) -> (loss, terms)``; ``nets``: list of modules in optimizer-group order."""
+def format_depth_metrics(metrics):
+    """The line train.py and depth_eval.py print: ``Depth: abs_diff ... a3 ...``."""
+    from .metrics import METRICS
+    return "Depth: " + " ".join(f"{k} {metrics[k]:.9f}" for k in METRICS)
+
+
+@torch.no_grad()
+def validate_depth(disp_net, loader, device, crop=True, median_scaling=True):
+    """Depth validation against ground truth: the mean over the validation images (those with a valid pixel) of the eight
+    metrics of dvf.metrics.depth_metrics, as a dict.  ``loader`` yields (frames [B,3,h,w], depth [B,Hg,Wg]) batches
+    (dataset.depth_validation_set(...).loader(b)).  The network runs in eval mode; its finest disparity is brought to the
+    ground truth's size bilinearly (dvf_resize_bilinear_fwd, scale h/Hg, w/Wg) and inverted, then one depth_metrics call per
+    batch; rows and the image count accumulate on the device and the pass synchronises once, at its end."""
+    from . import lib as L
+    from .metrics import METRICS, depth_metrics
+    was_training = disp_net.training
+    disp_net.eval()
+    total = torch.zeros(len(METRICS), device=device)
+    count = torch.zeros((), device=device)
+    for img, gt in loader:
+        img, gt = img.float().to(device).contiguous(), gt.float().to(device).contiguous()
+        disp = disp_net(img)
+        disp = (disp[0] if type(disp) in (list, tuple) else disp).contiguous()
+        b, _, h, w = disp.shape
+        hg, wg = gt.shape[1:]
+        up = torch.empty(b, hg, wg, device=device, dtype=torch.float32)
+        L.check(L.lib().dvf_resize_bilinear_fwd(L.dev(disp, "disparity"), L.dev(up), b, h, w, hg, wg, h / hg, w / wg, L.stream()),
+                "dvf_resize_bilinear_fwd")
+        depth = torch.empty_like(up)
+        L.check(L.lib().dvf_recip_fwd(L.dev(up), L.dev(depth), 0.0, up.numel(), L.stream()), "dvf_recip_fwd")
+        rows = depth_metrics(gt, depth, crop=crop, median_scaling=median_scaling)
+        keep = (rows[:, 8] > 0).float()
+        total += (rows[:, :len(METRICS)] * keep[:, None]).sum(0)
+        count += keep.sum()
+    means = (total / count.clamp(min=1.0)).tolist()                     # the pass's one synchronisation
+    disp_net.train(was_training)
+    return dict(zip(METRICS, means))
+
+
+def run_training(args, nets, loss_fn, lr, betas, weight_decay, term_names, ckpt_names, n_views=2, val_fn=None,
+                 depth_val_fn=None, depth_ckpt=None):
+    """Epoch loop.  ``loss_fn(batch) -> (loss, terms)``; ``nets``: list of modules in optimizer-group order.
+    ``depth_val_fn`` (rank 0, optional): returns the dict of ``validate_depth`` after every epoch; its line is printed and
+    ``depth_ckpt`` = (file name, module) is then saved on the best abs_rel instead of on the criterion of the other
+    checkpoints, which stays as it is."""
     rank, world, device = args._rank, args._world, args._device
     if getattr(args, "deterministic", False):
         from . import conv as _conv
@@ -224,7 +267,9 @@ def run_training(args, nets, loss_fn, lr, betas, weight_decay, term_names, ckpt_
     if world == 1 and not args.no_graph:
         step()                                                   # one eager step sizes every workspace
         runner = GraphedStep(step, [], warmup=1)
-    best = float("inf")
+    best = best_abs_rel = float("inf")
+    if depth_val_fn is not None:
+        ckpt_names = [c for c in ckpt_names if c[0] != depth_ckpt[0]]
     for epoch in range(args.epochs):
         acc.zero_()
         t0 = time.perf_counter()
@@ -259,5 +304,12 @@ def run_training(args, nets, loss_fn, lr, betas, weight_decay, term_names, ckpt_
             if score < best:
                 best = score
                 save_best(args.output_dir, ckpt_names)
+            if depth_val_fn is not None:
+                # eager launches between graph replays; a geometry first seen here gets its packed weights like any other
+                depth = depth_val_fn()
+                print(format_depth_metrics(depth) + " [BEST:{}]".format(depth["abs_rel"] < best_abs_rel), flush=True)
+                if depth["abs_rel"] < best_abs_rel:
+                    best_abs_rel = depth["abs_rel"]
+                    save_best(args.output_dir, [depth_ckpt])
     if world > 1:
         dist.destroy_process_group()

@@ -35,6 +35,7 @@ c_ip = ctypes.POINTER(ctypes.c_int)
 ROT_QUAT, PAD_BORDER, ALIGN_CORNERS, POSE_SE3, PIXEL_COORDS, CAFFE_ABSLOSS = 1, 2, 4, 8, 16, 32
 ACT_NONE, ACT_RELU, ACT_SIGMOID_AFFINE = 0, 1, 2
 MAX_VIEWS, MAX_SEGS = 4, 5
+DM_MEDIAN_SCALE, DM_RECLAMP = 1, 2
 
 # name -> (restype, argtypes); kept in one table so tests can check every declared symbol is exported
 SIGNATURES = {
@@ -100,6 +101,8 @@ SIGNATURES = {
     "dvf_bce_ones_fwd": (c_i, [c_fp, c_fp, c_fp, c_i64, c_i, c_fp]),
     "dvf_bce_ones_bwd": (c_i, [c_fp, c_fp, c_fp, c_i64, c_fp]),
     "dvf_adam_step": (c_i, [c_fp] * 4 + [c_i64, c_fp, c_i] + [c_f] * 5 + [c_fp]),
+    "dvf_depth_metrics_ws_floats": (c_i64, [c_i] * 3),
+    "dvf_depth_metrics": (c_i, [c_fp] * 4 + [c_i64] + [c_i] * 7 + [c_f] * 4 + [c_u32, c_fp]),
 }
 
 

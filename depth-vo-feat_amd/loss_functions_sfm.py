@@ -146,3 +146,14 @@ def compute_errors(gt, pred, crop=True):
         row = [err.mean(), (err / g).mean(), (err * err / g).mean()] + [(ratio < 1.25 ** e).float().mean() for e in (1, 2, 3)]
         totals += torch.stack([r.double().cpu() for r in row])
     return (totals / n).tolist()
+
+
+@torch.no_grad()
+def compute_errors_device(gt, pred, crop=True):
+    """``compute_errors`` on the device: the same six batch means [abs_diff, abs_rel, sq_rel, a1, a2, a3] from one
+    ``dvf.metrics.depth_metrics`` call (a few launches for the whole batch, exact lower median, no boolean gather, no sort)
+    and ONE host transfer, the ``.tolist()`` below.  Like the reference it divides by the batch size: an image without a
+    valid pixel contributes zeros here, where ``compute_errors`` fails on the median of an empty tensor."""
+    from dvf.metrics import depth_metrics
+    rows = depth_metrics(gt, pred, crop=crop)
+    return (rows[:, [0, 1, 2, 5, 6, 7]].double().sum(0) / gt.shape[0]).tolist()

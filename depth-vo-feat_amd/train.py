@@ -7,6 +7,8 @@ data is the seeded synthetic stream unless --data-root is given, multi-GPU is on
 instead of nn.DataParallel.  ``validate()`` (odometry L1 against the ground-truth relative poses of the test sequences,
 train.py:220-247) runs after every epoch when --val-root points at a KITTI-odometry tree (sequences/<seq>/image_2,
 poses/<seq>.txt) and then decides the best checkpoint like the reference; otherwise the best training loss does.
+With --val-depth-root the depth network is validated against ground-truth depth after every epoch as well (Eigen metrics,
+computed on the GPU) and best_depth_checkpoint.pth.tar follows the best abs_rel.
 
     python train.py -b 4 --epochs 2                       # 1 GPU
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py -b 4
@@ -50,6 +52,10 @@ parser.add_argument("-g", "--gpu-id", type=int, metavar="N", default=-1, help="a
 parser.add_argument("--output-dir", type=str, default="./checkpoints")
 parser.add_argument("--nb-ref-imgs", type=int, default=2, help="reference views (2 = temporal + stereo; 4 = 5-frame window)")
 parser.add_argument("--val-root", default=None, help="KITTI odometry tree for validate() on --test-sequences (train.py:220-247)")
+parser.add_argument("--val-depth-root", default=None, metavar="DIR",
+                    help="depth validation tree (val.txt, image/<stem>.png|jpg, depth/<stem>.npy in metres, 0 = no measurement): "
+                         "after every epoch rank 0 prints the Eigen depth metrics of the depth network against it "
+                         "(dvf.cli.validate_depth) and best_depth_checkpoint.pth.tar is saved on the best abs_rel")
 cli.add_common_flags(parser)
 
 
@@ -87,9 +93,15 @@ def main():
                                        shuffle=False)
         val_loader = torch.utils.data.DataLoader(val_set, batch_size=args.batch_size, shuffle=False, num_workers=0)
         val_fn = lambda: cli.validate(pose_exp_net, val_loader, args._device)      # noqa: E731
+    depth_kwargs = {}
+    if args.val_depth_root and args._rank == 0:
+        from dataset import depth_validation_set
+        depth_loader = depth_validation_set(args.val_depth_root, args.height, args.width).loader(args.batch_size)
+        depth_kwargs = {"depth_val_fn": lambda: cli.validate_depth(disp_net, depth_loader, args._device),
+                        "depth_ckpt": ("best_depth_checkpoint.pth.tar", disp_net)}
     cli.run_training(args, [disp_net, pose_exp_net], loss_fn, args.lr, (args.momentum, args.beta), args.weight_decay,
                      terms, [("best_vo_checkpoint.pth.tar", pose_exp_net), ("best_depth_checkpoint.pth.tar", disp_net)],
-                     n_views=max(2, args.nb_ref_imgs), val_fn=val_fn)
+                     n_views=max(2, args.nb_ref_imgs), val_fn=val_fn, **depth_kwargs)
 
 
 if __name__ == "__main__":

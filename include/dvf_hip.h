@@ -405,6 +405,31 @@ int dvf_adam_step(float *param, const float *grad, float *exp_avg, float *exp_av
                   int advance_step, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                   void *stream);
 
+/* ---------------------------------------------------------------- depth validation against ground truth
+ * Per-image masked depth error metrics with exact median scaling: the reference's compute_errors
+ * (loss_functions_sfm.py:80-116) plus the rmse / rmse_log columns of the Eigen protocol, as a few launches and no host
+ * synchronisation.  gt, pred [B,H,W] fp32 at the same size; out [B][12].  Per image:
+ *   valid = gt > gt_lo && gt < gt_hi && y1 <= y < y2 && x1 <= x < x2   (strict in gt: a NaN gt is invalid; the Garg crop of
+ *           :92-93 is the rectangle, an empty rectangle is legal)
+ *   p     = clamp(pred, clamp_lo, clamp_hi)                             (a NaN prediction stays NaN)
+ *   DVF_DM_MEDIAN_SCALE: s = fl(med(gt_valid) / med(p_valid)), p = fl(p * s); med = the LOWER median, the element of rank
+ *           (n-1)/2 (what torch.median returns), found exactly by a three-pass radix select on the bit patterns
+ *   DVF_DM_RECLAMP: p is clamped again after scaling (depth_eval.evaluate)
+ *   out row = [abs_diff, abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, n_valid, med_gt, med_pred, n_nan], means over the valid
+ *           pixels, a_e = share with max(g/p, p/g) < 1.25^e, medians before scaling, n_nan = valid pixels whose prediction
+ *           is NaN: with n_nan > 0 the eight metrics (and med_pred) are NaN; with n_valid == 0 the row is all zeros.
+ * ws: dvf_depth_metrics_ws_floats(B, H, W) floats, zeroed by the call itself.  Integer atomics and per-block partials added in
+ * a fixed order only: two runs are bit-identical.  No allocation, no synchronisation: graph-capturable.
+ * Checked on the host before anything is launched: DVF_ERR_INVALID_ARG for a null pointer, a non-positive size, ws_floats
+ * below the query, a rectangle outside [0,H] x [0,W] (or y1 > y2, x1 > x2), clamp_lo <= 0, clamp_lo > clamp_hi, gt_lo < 0,
+ * B * H * W >= 2^31 or B > 65535. */
+#define DVF_DM_MEDIAN_SCALE 1u
+#define DVF_DM_RECLAMP 2u
+int64_t dvf_depth_metrics_ws_floats(int B, int H, int W);
+int dvf_depth_metrics(const float *gt, const float *pred, float *out /* [B][12] */, float *ws, int64_t ws_floats, int B, int H,
+                      int W, int y1, int y2, int x1, int x2, float gt_lo, float gt_hi, float clamp_lo, float clamp_hi,
+                      uint32_t flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
