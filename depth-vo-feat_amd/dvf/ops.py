@@ -9,12 +9,19 @@ import torch
 
 from . import conv as _conv
 from . import lib as L
+from .conv import _c
 
 _WARNED_SRC_ATOMICS = False   # PhotoLossFn.backward: the deterministic-mode warning about source gradients has been given
 
 
-def _f32c(t):
-    return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
+def _grad_loss(gloss):
+    """The gradient of a 0-dim loss as the [1] float32 tensor the backward kernels read."""
+    return _c(gloss).reshape(1)
+
+
+def as_list(x):
+    """One map, or a tuple / list of maps (one per scale) as it is."""
+    return x if type(x) in (tuple, list) else [x]
 
 
 class InverseWarpFn(torch.autograd.Function):
@@ -22,7 +29,7 @@ class InverseWarpFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, img, depth, pose, K, Kinv, flags):
-        img, depth, pose, K, Kinv = map(_f32c, (img, depth, pose, K, Kinv))
+        img, depth, pose, K, Kinv = map(_c, (img, depth, pose, K, Kinv))
         B, C, H, W = img.shape
         out = torch.empty_like(img)
         L.check(L.lib().dvf_inverse_warp_fwd(L.dev(img, "img"), L.dev(depth, "depth"), L.dev(pose, "pose"),
@@ -47,7 +54,7 @@ class InverseWarpFn(torch.autograd.Function):
             (lib.dvf_inverse_warp_bwd, "dvf_inverse_warp_bwd")
         ws_floats = lib.dvf_inverse_warp_ordered_ws_floats(B, H, W) if ordered else lib.dvf_pose_ws_floats(1, B)
         ws = torch.empty(int(ws_floats), device=img.device) if need_pose else None
-        L.check(bwd(L.dev(img), L.dev(depth), L.dev(pose), L.dev(K), L.dev(Kinv), L.dev(_f32c(gout), "grad_out"), L.dev(g_img),
+        L.check(bwd(L.dev(img), L.dev(depth), L.dev(pose), L.dev(K), L.dev(Kinv), L.dev(_c(gout), "grad_out"), L.dev(g_img),
                     L.dev(g_depth), L.dev(g_pose), L.dev(ws), B, C, H, W, ctx.flags, L.stream()), what)
         return g_img, g_depth, g_pose, None, None, None
 
@@ -63,9 +70,9 @@ class PhotoLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tgt, depth, pose, K, Kinv, mask, flags, *srcs):
         flags, in_scale = flags if isinstance(flags, tuple) else (flags, 1.0)
-        tgt, depth, pose, K, Kinv = map(_f32c, (tgt, depth, pose, K, Kinv))
-        srcs = [_f32c(s) for s in srcs]
-        mask = _f32c(mask) if mask is not None else None
+        tgt, depth, pose, K, Kinv = map(_c, (tgt, depth, pose, K, Kinv))
+        srcs = [_c(s) for s in srcs]
+        mask = _c(mask) if mask is not None else None
         B, C, H, W = tgt.shape
         V = len(srcs)
         lib = L.lib()
@@ -103,7 +110,7 @@ class PhotoLossFn(torch.autograd.Function):
                           "feature maps) with float atomics, so the parameters trained through them are not bit-identical "
                           "from run to run", RuntimeWarning, stacklevel=2)
         ws = torch.empty(int(lib.dvf_photo_pose_ws_floats(B, H, W, V)), device=tgt.device) if need[2] else None
-        gl = _f32c(gloss).reshape(1)
+        gl = _grad_loss(gloss)
         # bwd = fwd (recompute) + grad depth + mask grads + grad target + RMW scatter into the source grads
         bwd_bytes = ctx.fwd_bytes + float(B * H * W) * (
             (4 if g_depth is not None else 0) + (4 * V if g_mask is not None else 0) +
@@ -126,8 +133,8 @@ class SsimL1LossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tgt, warped, mask, cfg):
         in_scale, alpha, c1, c2, view = cfg
-        tgt, warped = _f32c(tgt), _f32c(warped)
-        mask = _f32c(mask) if mask is not None else None
+        tgt, warped = _c(tgt), _c(warped)
+        mask = _c(mask) if mask is not None else None
         B, C, H, W = tgt.shape
         if warped.shape != tgt.shape:
             raise ValueError(f"warped {tuple(warped.shape)} does not match target {tuple(tgt.shape)}")
@@ -170,7 +177,7 @@ class SsimL1LossFn(torch.autograd.Function):
                                                         (4 if g_mask is not None else 0))
         with L.timed("ssim_bwd", 0.0, bwd_bytes):
             L.check(L.lib().dvf_ssim_loss_bwd(L.dev(tgt), L.dev(warped), L.dev(mask) + off if mask is not None else None,
-                                              ctx.m_stride, L.dev(_f32c(gloss).reshape(1), "grad_loss"), L.dev(g_warped),
+                                              ctx.m_stride, L.dev(_grad_loss(gloss), "grad_loss"), L.dev(g_warped),
                                               L.dev(g_tgt), L.dev(g_mask) + off if g_mask is not None else None,
                                               B, C, H, W, in_scale, alpha, c1, c2, L.stream()), "dvf_ssim_loss_bwd")
         return g_tgt, g_warped, g_mask.reshape(ctx.mask_shape) if g_mask is not None else None, None
@@ -199,8 +206,8 @@ class MinReprojLossFn(torch.autograd.Function):
                 raise ValueError(f"candidate {k} {tuple(y.shape)} does not match target {tuple(tgt.shape)}")
             if k >= V and ctx.needs_input_grad[3 + k]:
                 raise ValueError(f"identity candidate {k} requires a gradient: the auto-mask sources are constants")
-        tgt = _f32c(tgt)
-        cands = [_f32c(y) for y in cands]
+        tgt = _c(tgt)
+        cands = [_c(y) for y in cands]
         B, C, H, W = tgt.shape
         lib = L.lib()
         dev = tgt.device
@@ -231,7 +238,7 @@ class MinReprojLossFn(torch.autograd.Function):
         bwd_bytes = ctx.fwd_bytes + float(B * H * W) * 4 * C * n_grads
         with L.timed("minreproj_bwd", 0.0, bwd_bytes):
             L.check(L.lib().dvf_minreproj_bwd(L.dev(tgt), L.ptr_array(cands), V, auto_mask, select.data_ptr(),
-                                              L.dev(_f32c(gloss).reshape(1), "grad_loss"), L.dev(g_tgt), L.ptr_array(g_warped),
+                                              L.dev(_grad_loss(gloss), "grad_loss"), L.dev(g_tgt), L.ptr_array(g_warped),
                                               B, C, H, W, in_scale, alpha, c1, c2, L.stream()), "dvf_minreproj_bwd")
         return (g_tgt, None, None, *g_warped, *([None] * (len(cands) - V)))
 
@@ -245,7 +252,7 @@ class UpsampleIntFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, factor, recip_eps=None):
-        x = _f32c(x)
+        x = _c(x)
         if x.dim() != 4:
             raise ValueError(f"expected a [B,C,H,W] map, got {tuple(x.shape)}")
         B, C, H, W = x.shape
@@ -265,7 +272,7 @@ class UpsampleIntFn(torch.autograd.Function):
         out = ctx.saved_tensors[0] if recip else None
         gin = torch.empty((B, C, H, W), device=gout.device, dtype=torch.float32)
         with L.timed("upsample_int_bwd", 0.0, 4.0 * (gin.numel() + gout.numel() * (2 if recip else 1))):
-            L.check(L.lib().dvf_upsample_int_bwd(L.dev(_f32c(gout), "grad_out"), L.dev(out), L.dev(gin), B * C, H, W, factor,
+            L.check(L.lib().dvf_upsample_int_bwd(L.dev(_c(gout), "grad_out"), L.dev(out), L.dev(gin), B * C, H, W, factor,
                                                  int(recip), L.stream()), "dvf_upsample_int_bwd")
         return gin, None, None
 
@@ -276,7 +283,7 @@ class SmoothLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, scale_factor, *maps):
-        maps = [_f32c(m) for m in maps]
+        maps = [_c(m) for m in maps]
         lib = L.lib()
         out = torch.empty(1, device=maps[0].device)
         weights, w = [], 1.0
@@ -294,7 +301,7 @@ class SmoothLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss):
         maps = ctx.saved_tensors
-        gl = _f32c(gloss).reshape(1)
+        gl = _grad_loss(gloss)
         grads = []
         for i, (m, w) in enumerate(zip(maps, ctx.weights)):
             if not ctx.needs_input_grad[1 + i]:
@@ -321,7 +328,7 @@ class NormSmoothLossFn(torch.autograd.Function):
         scale_factor, in_scale, eps = cfg
         if not pairs or len(pairs) % 2:
             raise ValueError("NormSmoothLossFn takes (disparity, image) pairs")
-        disps, imgs = [_f32c(d) for d in pairs[0::2]], [_f32c(i) for i in pairs[1::2]]
+        disps, imgs = [_c(d) for d in pairs[0::2]], [_c(i) for i in pairs[1::2]]
         for d, i in zip(disps, imgs):
             if d.dim() != 4 or i.dim() != 4 or d.shape[1] != 1 or (d.shape[0],) + tuple(d.shape[2:]) != (i.shape[0],) + tuple(i.shape[2:]):
                 raise ValueError(f"disparity {tuple(d.shape)} does not match image {tuple(i.shape)}")
@@ -349,7 +356,7 @@ class NormSmoothLossFn(torch.autograd.Function):
         saved = ctx.saved_tensors
         disps, imgs, stats = saved[:n], saved[n:2 * n], saved[2 * n:]
         in_scale, eps = ctx.cfg
-        gl = _f32c(gloss).reshape(1)
+        gl = _grad_loss(gloss)
         grads = []
         for s, (d, i, st, w) in enumerate(zip(disps, imgs, stats, ctx.weights)):
             if not ctx.needs_input_grad[1 + 2 * s]:
@@ -370,7 +377,7 @@ class EdgeSmoothLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, inv_depth, img, in_scale, edge_k, weight):
-        inv_depth, img = _f32c(inv_depth), _f32c(img)
+        inv_depth, img = _c(inv_depth), _c(img)
         B, C, H, W = img.shape
         if tuple(inv_depth.shape) not in ((B, 1, H, W), (B, H, W)):
             raise ValueError(f"inv_depth {tuple(inv_depth.shape)} does not match image {tuple(img.shape)}")
@@ -389,7 +396,7 @@ class EdgeSmoothLossFn(torch.autograd.Function):
         B, C, H, W = img.shape
         g = torch.empty_like(inv_depth)
         in_scale, edge_k, weight = ctx.cfg
-        L.check(L.lib().dvf_edge_smooth_bwd(L.dev(inv_depth), L.dev(img), L.dev(_f32c(gloss).reshape(1), "grad_loss"), L.dev(g),
+        L.check(L.lib().dvf_edge_smooth_bwd(L.dev(inv_depth), L.dev(img), L.dev(_grad_loss(gloss), "grad_loss"), L.dev(g),
                                             B, C, H, W, in_scale, edge_k, weight, L.stream()), "dvf_edge_smooth_bwd")
         return g, None, None, None, None
 
@@ -399,7 +406,7 @@ class ExplainabilityLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, *masks):
-        masks = [_f32c(m) for m in masks]
+        masks = [_c(m) for m in masks]
         out = torch.empty(1, device=masks[0].device)
         partials = torch.empty(1024, device=masks[0].device)
         for i, m in enumerate(masks):
@@ -410,7 +417,7 @@ class ExplainabilityLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gloss):
-        gl = _f32c(gloss).reshape(1)
+        gl = _grad_loss(gloss)
         grads = []
         for i, m in enumerate(ctx.saved_tensors):
             if not ctx.needs_input_grad[i]:
@@ -428,7 +435,7 @@ class PoseVec2MatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vec, flags):
-        vec = _f32c(vec)
+        vec = _c(vec)
         n = vec.shape[0]
         out = torch.empty((n, 3, 4), device=vec.device, dtype=torch.float32)
         L.check(L.lib().dvf_pose_vec2mat_fwd(L.dev(vec, "vec"), L.dev(out), n, flags, L.stream()), "dvf_pose_vec2mat_fwd")
@@ -442,7 +449,7 @@ class PoseVec2MatFn(torch.autograd.Function):
         n = vec.shape[0]
         g = torch.empty_like(vec)
         ws = torch.empty(n * 12, device=vec.device)
-        L.check(L.lib().dvf_pose_vec2mat_bwd(L.dev(vec), L.dev(_f32c(gmat), "grad_out"), L.dev(g), L.dev(ws), n, ctx.flags,
+        L.check(L.lib().dvf_pose_vec2mat_bwd(L.dev(vec), L.dev(_c(gmat), "grad_out"), L.dev(g), L.dev(ws), n, ctx.flags,
                                              L.stream()), "dvf_pose_vec2mat_bwd")
         return g, None
 
@@ -452,7 +459,7 @@ class Pixel2CamFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, depth, Kinv):
-        depth, Kinv = _f32c(depth), _f32c(Kinv)
+        depth, Kinv = _c(depth), _c(Kinv)
         B, H, W = depth.shape
         cam = torch.empty((B, 3, H, W), device=depth.device, dtype=torch.float32)
         L.check(L.lib().dvf_pixel2cam_fwd(L.dev(depth, "depth"), L.dev(Kinv, "intrinsics_inv"), L.dev(cam), B, H, W,
@@ -466,7 +473,7 @@ class Pixel2CamFn(torch.autograd.Function):
         (Kinv,) = ctx.saved_tensors
         B, H, W = ctx.shape
         g = torch.empty((B, H, W), device=gcam.device, dtype=torch.float32)
-        L.check(L.lib().dvf_pixel2cam_bwd(L.dev(Kinv), L.dev(_f32c(gcam), "grad_out"), L.dev(g), B, H, W, L.stream()),
+        L.check(L.lib().dvf_pixel2cam_bwd(L.dev(Kinv), L.dev(_c(gcam), "grad_out"), L.dev(g), B, H, W, L.stream()),
                 "dvf_pixel2cam_bwd")
         return g, None
 
@@ -476,9 +483,9 @@ class Cam2PixelFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cam, rot, tr, flags):
-        cam = _f32c(cam)
-        rot = _f32c(rot) if rot is not None else None
-        tr = _f32c(tr).reshape(-1, 3) if tr is not None else None
+        cam = _c(cam)
+        rot = _c(rot) if rot is not None else None
+        tr = _c(tr).reshape(-1, 3) if tr is not None else None
         B, _, H, W = cam.shape
         grid = torch.empty((B, H, W, 2), device=cam.device, dtype=torch.float32)
         L.check(L.lib().dvf_cam2pixel_fwd(L.dev(cam, "cam_coords"), L.dev(rot, "proj_c2p_rot"), L.dev(tr, "proj_c2p_tr"),
@@ -494,7 +501,7 @@ class Cam2PixelFn(torch.autograd.Function):
         gcam = torch.empty_like(cam) if ctx.needs_input_grad[0] else None
         need_rt = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         ws = torch.empty((B, 12), device=cam.device) if need_rt else None
-        L.check(L.lib().dvf_cam2pixel_bwd(L.dev(cam), L.dev(rot), L.dev(tr), L.dev(_f32c(ggrid), "grad_out"), L.dev(gcam),
+        L.check(L.lib().dvf_cam2pixel_bwd(L.dev(cam), L.dev(rot), L.dev(tr), L.dev(_c(ggrid), "grad_out"), L.dev(gcam),
                                           L.dev(ws), B, H, W, ctx.flags, L.stream()), "dvf_cam2pixel_bwd")
         g_rot = ws[:, 3:].reshape(B, 3, 3) if (rot is not None and ctx.needs_input_grad[1]) else None
         g_tr = ws[:, :3].reshape(B, 3, 1) if (tr is not None and ctx.needs_input_grad[2]) else None

@@ -10,6 +10,7 @@ import torch
 import loss_functions as LF
 import loss_functions_sfm as LS
 from dvf import lib as L
+from dvf.appearance import appearance_term
 from dvf.conv import reciprocal
 
 
@@ -64,6 +65,21 @@ def _identity_share(counts, n_views):
     return counts[n_views:2 * n_views].sum() / counts.sum()
 
 
+def _feature_maps(feat_extractor, L2, R2, R1, frozen=False):
+    """One extractor pass over the three frames (unsupervise.py:104-107); ``frozen``: no graph, no weight gradients."""
+    with torch.set_grad_enabled(torch.is_grad_enabled() and not frozen):
+        feat = feat_extractor(torch.cat((L2, R2, R1), dim=0))
+    b = R2.size(0)
+    return feat[:b], feat[b:2 * b], feat[2 * b:]
+
+
+def _smoothness(normalized, disparities, depths, img, scale_factor=1.0, img_scale=1.0):
+    """Second-order smoothness of the depths, or ``normalized``: edge-aware first-order, of the mean-normalised disparities."""
+    if normalized:
+        return LS.normalized_smooth_loss(disparities, img, scale_factor, img_scale)
+    return LS.smooth_loss(depths, scale_factor)
+
+
 def unsupervise_losses(depth_net, pose_net, batch, feat_extractor=None, img_scale=0.004, smooth_weight=10.0,
                        feat_weight=0.1, depth_eps=1e-4, ssim_weight=0.0, ssim_c1=1e-4, ssim_c2=9e-4, min_reprojection=False,
                        auto_mask=False, normalized_smoothness=False):
@@ -84,18 +100,13 @@ def unsupervise_losses(depth_net, pose_net, batch, feat_extractor=None, img_scal
                                                   ssim_weight=ssim_weight, ssim_c1=ssim_c1, ssim_c2=ssim_c2,
                                                   min_reprojection=min_reprojection, auto_mask=auto_mask,
                                                   selection_counts=counts)
-    if normalized_smoothness:
-        smooth = LF.normalized_smooth_loss(inv_depth, R2, img_scale=img_scale)
-    else:
-        smooth = LF.smooth_loss(depth.unsqueeze(1))                # :102
+    smooth = _smoothness(normalized_smoothness, inv_depth, depth.unsqueeze(1), R2, img_scale=img_scale)    # :102
     terms = {"img": img_loss.detach(), "smooth": smooth.detach()}
     if auto_mask:
         terms["automask"] = _identity_share(counts[0], 2)
     loss = img_loss + smooth_weight * smooth
     if feat_extractor is not None:
-        b = R2.size(0)
-        feat = feat_extractor(torch.cat((L2, R2, R1), dim=0))      # :104-105
-        f_L2, f_R2, f_R1 = feat[:b], feat[b:2 * b], feat[2 * b:]  # :107
+        f_L2, f_R2, f_R1 = _feature_maps(feat_extractor, L2, R2, R1)                               # :104-107
         feat_loss = LF.photometric_reconstruction_loss(f_R2, f_R1, f_L2, depth, T_2to1, batch["T_R2L"], batch["K"],
                                                        batch["Kinv"])                              # :109
         loss = img_loss + feat_weight * feat_loss + smooth_weight * smooth                          # :111
@@ -109,9 +120,8 @@ def depth_only_losses(depth_net, batch, img_scale=0.004, smooth_weight=10.0, dep
     into the right one with the fixed baseline pose) + 10 * smooth -- unsupervise.py:94-102 without the pose network."""
     R2, L2 = batch["img_R2"], batch["img_L2"]
     depth = reciprocal(depth_net(R2)[0], depth_eps)                # [B,1,H,W]
-    from dvf.ops import PhotoLossFn
-    photo = PhotoLossFn.apply(R2, depth.squeeze(1), batch["T_R2L"].unsqueeze(0).contiguous(), batch["K"], batch["Kinv"], None,
-                              (0, float(img_scale)), L2)
+    photo = appearance_term(None, R2, (L2,), depth.squeeze(1), (batch["T_R2L"],), batch["K"], batch["Kinv"], 0, img_scale,
+                            pose_vb6=batch["T_R2L"].unsqueeze(0).contiguous())
     smooth = LF.smooth_loss(depth)
     loss = photo + smooth_weight * smooth
     return loss, {"img": photo.detach(), "smooth": smooth.detach(), "total": loss.detach()}
@@ -153,10 +163,7 @@ def train_sfm_losses(disp_net, pose_exp_net, batch, w1=1.0, w2=0.0, w3=0.1, smoo
                                             rotation_mode, padding_mode, ssim_weight=ssim_weight, ssim_c1=ssim_c1,
                                             ssim_c2=ssim_c2, min_reprojection=min_reprojection, auto_mask=auto_mask,
                                             selection_counts=counts)                               # :191
-    if normalized_smoothness:
-        l3 = LS.normalized_smooth_loss(disparities, tgt, smooth_factor)
-    else:
-        l3 = LS.smooth_loss(depth, smooth_factor)                  # :200
+    l3 = _smoothness(normalized_smoothness, disparities, depth, tgt, smooth_factor)                # :200
     l4 = torch.nn.functional.mse_loss(pose[:, 1], batch["T_R2L"])  # :201  (24 floats: left to torch)
     loss = w1 * l1 + w3 * l3 + l4
     terms = {"photo": l1.detach(), "smooth": l3.detach(), "lr": l4.detach()}
@@ -167,9 +174,7 @@ def train_sfm_losses(disp_net, pose_exp_net, batch, w1=1.0, w2=0.0, w3=0.1, smoo
         loss = loss + w2 * l2
         terms["exp"] = l2.detach()
     if feat_extractor is not None:
-        b = tgt.size(0)
-        feat = feat_extractor(torch.cat((refs[1], tgt, refs[0]), dim=0))    # (L2, R2, R1) as unsupervise.py:104-105
-        f_L2, f_R2, f_R1 = feat[:b], feat[b:2 * b], feat[2 * b:]
+        f_L2, f_R2, f_R1 = _feature_maps(feat_extractor, refs[1], tgt, refs[0])
         lf = LF.photometric_reconstruction_loss(f_R2, f_R1, f_L2, depth[0].squeeze(1), pose[:, 0], pose[:, 1], batch["K"],
                                                 batch["Kinv"], rotation_mode, padding_mode)
         loss = loss + feat_weight * lf
@@ -186,15 +191,13 @@ def unsupervise_dvo_losses(depth_net, pose_net, batch, img_scale=0.004, smooth_w
     DVF_POSE_SE3 | DVF_PIXEL_COORDS front end.  batch["T_R2L"] must be in the se(3) order (w, u), i.e. (0,0,0,Tx,0,0)
     as the reference dataset writes it (data/dataset_builder.py:155).  normalized_smoothness (extension): as in
     unsupervise_losses."""
-    from dvf.ops import PhotoLossFn
     R2, R1, L2 = batch["img_R2"], batch["img_R1"], batch["img_L2"]
     (_, T_2to1), disps = _side_by_side(lambda: _pose_only(pose_net, (R2, R1)), lambda: depth_net(R2))
     inv_depth = disps[0]
     depth = reciprocal(inv_depth, depth_eps)                               # [B,1,H,W]
-    pose = torch.stack((batch["T_R2L"], T_2to1), dim=0)                    # [V=2,B,6]: view 0 = left image, view 1 = R1
-    photo = PhotoLossFn.apply(R2, depth.squeeze(1), pose, batch["K"], batch["Kinv"], None,
-                              (L.POSE_SE3 | L.PIXEL_COORDS, float(img_scale)), L2, R1)
-    smooth = LF.normalized_smooth_loss(inv_depth, R2, img_scale=img_scale) if normalized_smoothness else LF.smooth_loss(depth)
+    photo = appearance_term(None, R2, (L2, R1), depth.squeeze(1), (batch["T_R2L"], T_2to1), batch["K"], batch["Kinv"],
+                            L.POSE_SE3 | L.PIXEL_COORDS, img_scale)        # view 0 = left image, view 1 = R1
+    smooth = _smoothness(normalized_smoothness, inv_depth, depth, R2, img_scale=img_scale)
     loss = photo + smooth_weight * smooth
     return loss, {"photo": photo.detach(), "smooth": smooth.detach(), "total": loss.detach()}
 
@@ -217,10 +220,7 @@ def paper_losses(depth_net, pose_net, batch, feat_extractor=None, img_scale=0.00
     loss = photo + smooth_weight * smooth
     terms = {"photo": photo.detach(), "smooth": smooth.detach()}
     if feat_extractor is not None:
-        b = R2.size(0)
-        with torch.no_grad():                                              # frozen extractor: no graph, no weight gradients
-            feat = feat_extractor(torch.cat((L2, R2, R1), dim=0))
-        f_L2, f_R2, f_R1 = feat[:b], feat[b:2 * b], feat[2 * b:]
+        f_L2, f_R2, f_R1 = _feature_maps(feat_extractor, L2, R2, R1, frozen=True)
         lf = LC.abs_warp_loss(f_R2, (f_L2, f_R1), depth, poses, batch["K"], batch["Kinv"])
         loss = loss + feat_weight * lf
         terms["feat"] = lf.detach()

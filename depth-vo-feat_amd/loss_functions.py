@@ -1,9 +1,8 @@
 """Drop-in for the reference's ``pytorch_version/loss_functions.py`` (single-scale API of
 ``unsupervise.py``) on MI355X: each loss is a fused HIP kernel pair (forward / backward)."""
-import torch
-
 from dvf import lib as _L
-from dvf.ops import PhotoLossFn, SmoothLossFn
+from dvf.appearance import appearance_term
+from dvf.ops import NormSmoothLossFn, SmoothLossFn, as_list
 from inverse_warp import inverse_warp, check_sizes  # noqa: F401  (re-exported like the reference's copy)
 
 
@@ -27,35 +26,14 @@ def photometric_reconstruction_loss(img_R2, img_R1, img_L2, depth, T_2to1, T_R2L
     assert(intrinsics_inv.size() == intrinsics.size())
     if auto_mask and not min_reprojection:
         raise ValueError("auto_mask needs min_reprojection=True")
-    flags = _L.geom_flags(rotation_mode, padding_mode, align_corners)
-    if min_reprojection:
-        from dvf.ops import InverseWarpFn, MinReprojLossFn
-        warped = [InverseWarpFn.apply(src, depth, T, intrinsics, intrinsics_inv, flags)
-                  for src, T in ((img_R1, T_2to1), (img_L2, T_R2L))]
-        cfg = (float(img_scale), float(ssim_weight), float(ssim_c1), float(ssim_c2), bool(auto_mask))
-        loss, _, counts = MinReprojLossFn.apply(img_R2, cfg, 2, *warped, *((img_R1, img_L2) if auto_mask else ()))
-        if selection_counts is not None:
-            selection_counts.append(counts)
-        return loss
-    if ssim_weight > 0:
-        from dvf.ops import InverseWarpFn, SsimL1LossFn
-        cfg = (float(img_scale), float(ssim_weight), float(ssim_c1), float(ssim_c2), None)
-        loss = 0
-        for src, T in ((img_R1, T_2to1), (img_L2, T_R2L)):
-            warped = InverseWarpFn.apply(src, depth, T, intrinsics, intrinsics_inv, flags)
-            loss = loss + SsimL1LossFn.apply(img_R2, warped, None, cfg)
-        return loss
-    pose = torch.stack((T_2to1, T_R2L), dim=0)                 # [V=2, B, 6]
-    if img_scale != 1.0:
-        flags = (flags, float(img_scale))
-    return PhotoLossFn.apply(img_R2, depth, pose, intrinsics, intrinsics_inv, None, flags, img_R1, img_L2)
+    return appearance_term(None, img_R2, (img_R1, img_L2), depth, (T_2to1, T_R2L), intrinsics, intrinsics_inv,
+                           _L.geom_flags(rotation_mode, padding_mode, align_corners), img_scale, None, ssim_weight, ssim_c1,
+                           ssim_c2, min_reprojection, auto_mask, selection_counts)
 
 
 def smooth_loss(pred_map, scale_factor=1):
     """Second-order smoothness of one map or a list of maps (reference loss_functions.py:23-41)."""
-    if type(pred_map) not in [tuple, list]:
-        pred_map = [pred_map]
-    return SmoothLossFn.apply(float(scale_factor), *pred_map)
+    return SmoothLossFn.apply(float(scale_factor), *as_list(pred_map))
 
 
 def normalized_smooth_loss(disp, img, img_scale=1.0, eps=1e-7):
@@ -63,5 +41,4 @@ def normalized_smooth_loss(disp, img, img_scale=1.0, eps=1e-7):
     reference has no such term: parity unpinned, tests/normsmooth_ref.py is the definition): with n = disp / (mean over the
     image of disp + eps) and I = img_scale * img, mean(exp(-mean_c |dx I|) |dx n|) + mean(exp(-mean_c |dy I|) |dy n|).
     disp [B,1,H,W], img [B,C,H,W]; only disp receives a gradient.  monodepth2 weighs the term with 1e-3."""
-    from dvf.ops import NormSmoothLossFn
     return NormSmoothLossFn.apply((1.0, float(img_scale), float(eps)), disp, img)

@@ -13,20 +13,17 @@ These functions have no counterpart in the reference's Python files and Caffe ca
 is UNPINNED -- the kernels are tested against ``oracle/``'s restatement of the layer sources and the oracle against
 finite differences.  The geometry is the Caffe chain (se(3) exponential map, pixel-coordinate warp) of
 ``unsupervise_dvo.py``."""
-import torch
-
 from dvf import lib as _L
-from dvf.ops import EdgeSmoothLossFn, PhotoLossFn
+from dvf.appearance import appearance_term
+from dvf.ops import EdgeSmoothLossFn
 
 
 def abs_warp_loss(tgt, srcs, depth, poses_se3, intrinsics, intrinsics_inv, img_scale=1.0):
     """sum over the views of AbsLoss(warp(src_v), tgt): ``warp_error_LR`` + ``warp_error_R12``
     (train.prototxt:4428-4446) when called with (left image, previous right image) and (T_R2L, T_2to1), and
     ``warp_feat_error`` (:5571-5588) on feature maps.  poses_se3: list of [B,6] se(3) vectors (w, u)."""
-    pose = torch.stack(list(poses_se3), dim=0)
     flags = _L.POSE_SE3 | _L.PIXEL_COORDS | _L.CAFFE_ABSLOSS
-    d = depth[:, 0] if depth.dim() == 4 else depth
-    return PhotoLossFn.apply(tgt, d, pose, intrinsics, intrinsics_inv, None, (flags, float(img_scale)), *srcs)
+    return appearance_term(None, tgt, srcs, depth, poses_se3, intrinsics, intrinsics_inv, flags, img_scale)
 
 
 def edge_aware_smooth_loss(inv_depth, img, img_scale=1.0, edge_k=0.33, weight=1.0):

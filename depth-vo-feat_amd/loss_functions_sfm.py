@@ -2,8 +2,9 @@
 import torch
 
 from dvf import lib as _L
+from dvf.appearance import appearance_term
 from dvf.conv import area_downsample, reciprocal
-from dvf.ops import ExplainabilityLossFn, PhotoLossFn, SmoothLossFn, UpsampleIntFn
+from dvf.ops import ExplainabilityLossFn, NormSmoothLossFn, SmoothLossFn, UpsampleIntFn, as_list
 
 
 def photometric_reconstruction_loss(tgt_img, ref_imgs, intrinsics, intrinsics_inv, depth, explainability_mask, pose,
@@ -29,10 +30,7 @@ def photometric_reconstruction_loss(tgt_img, ref_imgs, intrinsics, intrinsics_in
     that ``full_resolution`` brought to the input resolution runs every mode above at that resolution for every scale."""
     if auto_mask and not min_reprojection:
         raise ValueError("auto_mask needs min_reprojection=True")
-    if type(explainability_mask) not in [tuple, list]:
-        explainability_mask = [explainability_mask]
-    if type(depth) not in [list, tuple]:
-        depth = [depth]
+    explainability_mask, depth = as_list(explainability_mask), as_list(depth)
     assert(pose.size(1) == len(ref_imgs))
     if min_reprojection and any(m is not None for m in explainability_mask):
         raise ValueError("min_reprojection does not take an explainability mask: pass None for every scale")
@@ -47,23 +45,9 @@ def photometric_reconstruction_loss(tgt_img, ref_imgs, intrinsics, intrinsics_in
         refs_s = [area_downsample(r, (h, w)) for r in ref_imgs]          # :19
         k_s = torch.cat((intrinsics[:, 0:2] / downscale, intrinsics[:, 2:]), dim=1)               # :20
         kinv_s = torch.cat((intrinsics_inv[:, :, 0:2] * downscale, intrinsics_inv[:, :, 2:]), dim=2)   # :21
-        if min_reprojection:
-            from dvf.ops import InverseWarpFn, MinReprojLossFn
-            warped = [InverseWarpFn.apply(ref_s, d[:, 0], pose[:, v], k_s, kinv_s, flags) for v, ref_s in enumerate(refs_s)]
-            cfg = (1.0, float(ssim_weight), float(ssim_c1), float(ssim_c2), bool(auto_mask))
-            term, _, counts = MinReprojLossFn.apply(tgt_s, cfg, len(refs_s), *warped, *(refs_s if auto_mask else ()))
-            if selection_counts is not None:
-                selection_counts.append(counts)
-            loss = loss + term
-            continue
-        if ssim_weight > 0:
-            from dvf.ops import InverseWarpFn, SsimL1LossFn
-            for v, ref_s in enumerate(refs_s):
-                warped = InverseWarpFn.apply(ref_s, d[:, 0], pose[:, v], k_s, kinv_s, flags)
-                loss = loss + SsimL1LossFn.apply(tgt_s, warped, mask, (1.0, float(ssim_weight), float(ssim_c1), float(ssim_c2),
-                                                                        v if mask is not None else None))
-            continue
-        loss = loss + PhotoLossFn.apply(tgt_s, d[:, 0], pose_vb6, k_s, kinv_s, mask, flags, *refs_s)
+        loss = appearance_term(loss, tgt_s, refs_s, d, (pose[:, v] for v in range(len(refs_s))), k_s, kinv_s, flags,
+                               1.0, mask, ssim_weight, ssim_c1, ssim_c2, min_reprojection, auto_mask, selection_counts,
+                               pose_vb6=pose_vb6)
     if check_nan:
         assert((loss == loss).item() == 1)
     return loss
@@ -76,8 +60,7 @@ def full_resolution(maps, out_hw, recip_eps=None):
     disparity -> depth, fused into the same pass.  A map already at (H, W) is returned as it is (through ``reciprocal``
     with ``recip_eps``).  Gradients reach the coarse maps.  Any other size ratio raises ValueError.  Returns a list."""
     H, W = int(out_hw[0]), int(out_hw[1])
-    if type(maps) not in [tuple, list]:
-        maps = [maps]
+    maps = as_list(maps)
     factors = []
     for m in maps:                       # every size is checked before the first kernel runs
         h, w = m.shape[2:]
@@ -97,16 +80,12 @@ def full_resolution(maps, out_hw, recip_eps=None):
 
 def explainability_loss(mask):
     """sum_s BCE(mask_s, 1)  (reference loss_functions_sfm.py:49-56)."""
-    if type(mask) not in [tuple, list]:
-        mask = [mask]
-    return ExplainabilityLossFn.apply(*mask)
+    return ExplainabilityLossFn.apply(*as_list(mask))
 
 
 def smooth_loss(pred_map, scale_factor):
     """Second-order smoothness over a list of maps, weight divided by ``scale_factor`` per scale (:59-77)."""
-    if type(pred_map) not in [tuple, list]:
-        pred_map = [pred_map]
-    return SmoothLossFn.apply(float(scale_factor), *pred_map)
+    return SmoothLossFn.apply(float(scale_factor), *as_list(pred_map))
 
 
 def normalized_smooth_loss(disparities, tgt_img, scale_factor=2.0, img_scale=1.0, eps=1e-7):
@@ -116,11 +95,8 @@ def normalized_smooth_loss(disparities, tgt_img, scale_factor=2.0, img_scale=1.0
     with I = img_scale * tgt_img brought to the scale's size by ``area_downsample`` (a map at the image's own size takes the
     image as it is).  Only the disparities receive a gradient.  dvf.ops.NormSmoothLossFn: one forward pass and one backward
     launch per scale.  monodepth2 weighs the term with 1e-3."""
-    from dvf.ops import NormSmoothLossFn
-    if type(disparities) not in [tuple, list]:
-        disparities = [disparities]
     pairs = []
-    for d in disparities:
+    for d in as_list(disparities):
         pairs += [d, area_downsample(tgt_img, tuple(d.shape[2:]))]
     return NormSmoothLossFn.apply((float(scale_factor), float(img_scale), float(eps)), *pairs)
 
