@@ -79,6 +79,25 @@ class pose_framework_KITTI(data.Dataset):
         return len(self.samples)
 
 
+def odometry_sequences(root, sequence_set, img_height, img_width):
+    """The sequences of ``sequence_set`` under ``root`` one by one, for ``dvf.cli.validate_odometry``: a list of (name,
+    pairs, poses) in directory order.  ``pairs`` is ``pose_framework_KITTI(root, [name], shuffle=False)``: its sample i is
+    the frame pair (i, i + 1) in ``validate()``'s layout, in frame order; ``poses`` is the ground truth of ``poses/<name>.txt``
+    as [n,3,4] float64 (``read_scene_data`` keeps float32, enough for a relative pose but not for a trajectory of kilometres),
+    one pose per frame."""
+    names = set()
+    for seq in sequence_set:
+        names |= set(os.path.basename(d) for d in glob.glob(os.path.join(root, "sequences", seq)) if os.path.isdir(d))
+    out = []
+    for name in sorted(names):
+        pairs = pose_framework_KITTI(root, [name], img_height=img_height, img_width=img_width, shuffle=False)
+        poses = np.genfromtxt(os.path.join(root, "poses", f"{name}.txt"), dtype=np.float64).reshape(-1, 3, 4)
+        if len(pairs) != poses.shape[0] - 1:
+            raise ValueError(f"sequence {name}: {len(pairs) + 1} frames but {poses.shape[0]} ground-truth poses")
+        out.append((name, pairs, poses))
+    return out
+
+
 class DepthValidationSet(data.Dataset):
     """Frames with ground-truth depth for ``dvf.cli.validate_depth``.  Layout: ``root/val.txt`` holds one stem per line,
     ``root/image/<stem>.png|jpg`` the frame and ``root/depth/<stem>.npy`` a float32 [Hg,Wg] map in metres with 0 for no

@@ -3,6 +3,7 @@ synthetic data stream, the step loop with device-side loss accumulation, checkpo
 
 Data: the seeded synthetic stream that the benchmark uses by default; with ``--data-root`` the stereo-sequence listing
 of the reference's un_dataset.py is read through this build's PIL-based ``un_dataset.dataset``."""
+import math
 import os
 import time
 
@@ -197,12 +198,100 @@ def validate_depth(disp_net, loader, device, crop=True, median_scaling=True):
     return dict(zip(METRICS, means))
 
 
+POSE_CONVENTIONS = ("se3", "euler")
+
+
+def format_odometry(metrics, name=None):
+    """The line train.py and odometry_eval.py print: ``Odometry: t_err <%> r_err <deg/100m> segments <count>``, with
+    ``seq <name>`` appended for one sequence of a pass."""
+    line = f"Odometry: t_err {metrics['t_err']:.12g} r_err {metrics['r_err']:.12g} segments {metrics['segments']}"
+    return line if name is None else f"{line} seq {name}"
+
+
+@torch.no_grad()
+def validate_odometry(pose_net, sequences, device, batch_size, convention="se3", output_dir=None, keep=False):
+    """Trajectory validation against ground truth: the KITTI odometry errors (tools/evaluation_tools.py:452-508) of the pose
+    network's chained trajectory over ``sequences`` = dataset.odometry_sequences(...), as
+    {"t_err": percent, "r_err": degrees per 100 m, "segments": count, "per_sequence": {name: the same three + "path_length"}}.
+
+    Per sequence, batches of consecutive frame pairs go through the network as in ``validate()`` (eval mode, ``pose_net(later,
+    [earlier, earlier])``, output 0); dvf_pose_vec2mat_fwd writes every batch's matrices into one device buffer for all
+    sequences, then one dvf.odometry.chain_poses and one sequence_errors per sequence that accumulates into one summary.
+    Everything stays on the device and the pass synchronises once, at its end.  No scale alignment.
+
+    ``convention`` names how the six outputs are read, because the reference disagrees with itself: "se3" = (w, u) through the
+    se(3) exponential map, what ``validate()`` scores (train.py:229-231); "euler" = (t, r-euler), what train.py's photometric
+    loss trains them as (inverse_warp.py:141-157).  ``output_dir``: writes <name>.txt, one KITTI pose line per frame
+    (odometry_eval.save_result_poses' format), after the synchronisation.  ``keep``: the result also carries "rel" ([N,4,4]
+    fp32), "world" ([N+S,3,4] fp64) and "offsets" as chain_poses takes and returns them."""
+    from . import lib as L
+    from .odometry import chain_poses, sequence_errors
+    if convention not in POSE_CONVENTIONS:
+        raise ValueError(f"convention must be one of {POSE_CONVENTIONS}, got {convention!r}")
+    if not sequences:
+        raise ValueError("validate_odometry: no sequence to evaluate")
+    flags = L.POSE_SE3 if convention == "se3" else 0
+    was_training = pose_net.training
+    pose_net.eval()
+    offsets = [0]
+    for _, pairs, _ in sequences:
+        offsets.append(offsets[-1] + len(pairs))
+    N = offsets[-1]
+    rel = torch.zeros(N, 4, 4, device=device, dtype=torch.float32)
+    mats = torch.empty(N, 3, 4, device=device, dtype=torch.float32)
+    k = 0
+    for _, pairs, _ in sequences:
+        for data, _ in torch.utils.data.DataLoader(pairs, batch_size=batch_size, shuffle=False, num_workers=0):
+            data = data.float().to(device)
+            tgt, ref = data[:, :3].contiguous(), data[:, 3:].contiguous()
+            _, pose = pose_net(tgt, [ref, ref])
+            vec = pose[:, 0].reshape(-1, 6).contiguous()
+            b = vec.shape[0]
+            # (the kernel's rows are 12 floats apart: the batches land side by side in mats, rel gets its fourth row below)
+            L.check(L.lib().dvf_pose_vec2mat_fwd(L.dev(vec, "pose"), mats.data_ptr() + k * 48, b, flags, L.stream()),
+                    "dvf_pose_vec2mat_fwd")
+            k += b
+    rel[:, :3] = mats
+    rel[:, 3, 3] = 1.0
+    world = chain_poses(rel, offsets)
+    summary = torch.zeros(4, device=device, dtype=torch.float64)
+    per = []
+    for s, (_, _, poses) in enumerate(sequences):
+        gt = torch.from_numpy(poses).to(device=device, dtype=torch.float64).contiguous()
+        rows, _ = sequence_errors(gt, world[offsets[s] + s:offsets[s + 1] + s + 1], summary)
+        per.append(torch.stack([rows[:, 2].sum(), rows[:, 1].sum(), rows[:, 5].sum(), summary[3]]))
+    flat = torch.cat([summary[:3]] + per).tolist()                      # the pass's one synchronisation
+    pose_net.train(was_training)
+
+    def metrics(t_sum, r_sum, count):
+        nan = float("nan")
+        return {"t_err": 100.0 * t_sum / count if count else nan, "r_err": r_sum / count * 180.0 / math.pi * 100.0 if count else nan,
+                "segments": int(count)}
+
+    out = metrics(*flat[:3])
+    out["per_sequence"] = {}
+    for s, (name, _, _) in enumerate(sequences):
+        out["per_sequence"][name] = dict(metrics(*flat[3 + 4 * s:6 + 4 * s]), path_length=flat[6 + 4 * s])
+    if output_dir is not None:
+        os.makedirs(output_dir, exist_ok=True)
+        host = world.cpu().numpy()
+        for s, (name, _, _) in enumerate(sequences):
+            with open(os.path.join(output_dir, f"{name}.txt"), "w") as f:
+                for p in host[offsets[s] + s:offsets[s + 1] + s + 1]:
+                    f.write(" ".join(str(v) for v in p.reshape(12)) + "\n")
+    if keep:
+        out.update(rel=rel, world=world, offsets=offsets)
+    return out
+
+
 def run_training(args, nets, loss_fn, lr, betas, weight_decay, term_names, ckpt_names, n_views=2, val_fn=None,
-                 depth_val_fn=None, depth_ckpt=None):
+                 depth_val_fn=None, depth_ckpt=None, odometry_val_fn=None, odometry_ckpt=None):
     """Epoch loop.  ``loss_fn(batch) -> (loss, terms)``; ``nets``: list of modules in optimizer-group order.
     ``depth_val_fn`` (rank 0, optional): returns the dict of ``validate_depth`` after every epoch; its line is printed and
     ``depth_ckpt`` = (file name, module) is then saved on the best abs_rel instead of on the criterion of the other
-    checkpoints, which stays as it is."""
+    checkpoints, which stays as it is.  ``odometry_val_fn`` (rank 0, optional): returns the dict of ``validate_odometry``
+    after every epoch; its line is printed and ``odometry_ckpt`` = (file name, module), a file of its own, is saved on the
+    best t_err."""
     rank, world, device = args._rank, args._world, args._device
     if getattr(args, "deterministic", False):
         from . import conv as _conv
@@ -267,7 +356,7 @@ def run_training(args, nets, loss_fn, lr, betas, weight_decay, term_names, ckpt_
     if world == 1 and not args.no_graph:
         step()                                                   # one eager step sizes every workspace
         runner = GraphedStep(step, [], warmup=1)
-    best = best_abs_rel = float("inf")
+    best = best_abs_rel = best_t_err = float("inf")
     if depth_val_fn is not None:
         ckpt_names = [c for c in ckpt_names if c[0] != depth_ckpt[0]]
     for epoch in range(args.epochs):
@@ -311,5 +400,11 @@ def run_training(args, nets, loss_fn, lr, betas, weight_decay, term_names, ckpt_
                 if depth["abs_rel"] < best_abs_rel:
                     best_abs_rel = depth["abs_rel"]
                     save_best(args.output_dir, [depth_ckpt])
+            if odometry_val_fn is not None:
+                odo = odometry_val_fn()
+                print(format_odometry(odo) + " [BEST:{}]".format(odo["t_err"] < best_t_err), flush=True)
+                if odo["t_err"] < best_t_err:
+                    best_t_err = odo["t_err"]
+                    save_best(args.output_dir, [odometry_ckpt])
     if world > 1:
         dist.destroy_process_group()

@@ -103,6 +103,9 @@ SIGNATURES = {
     "dvf_adam_step": (c_i, [c_fp] * 4 + [c_i64, c_fp, c_i] + [c_f] * 5 + [c_fp]),
     "dvf_depth_metrics_ws_floats": (c_i64, [c_i] * 3),
     "dvf_depth_metrics": (c_i, [c_fp] * 4 + [c_i64] + [c_i] * 7 + [c_f] * 4 + [c_u32, c_fp]),
+    "dvf_pose_chain": (c_i, [c_fp, c_ip, c_i, c_fp, c_fp]),
+    "dvf_odometry_errors_ws_doubles": (c_i64, [c_i]),
+    "dvf_odometry_errors": (c_i, [c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_fp, c_i64, c_fp]),
 }
 
 

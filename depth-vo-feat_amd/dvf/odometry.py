@@ -1,0 +1,90 @@
+"""Odometry evaluation on the device (csrc/odometry.hip, ``dvf_pose_chain`` / ``dvf_odometry_errors`` of include/dvf_hip.h):
+the chained camera-to-world trajectory of relative poses and the KITTI segment errors against ground truth, in fp64.
+
+The definition is odometry_eval.py's numpy ``se3_cam2world`` / ``sequence_errors`` / ``overall_error`` for dense trajectories
+(frame i = row i of both).  Nothing here synchronises; every result is ordered on the current stream."""
+import torch
+
+from . import lib as L
+
+SEGMENT_LENGTHS = (100, 200, 300, 400, 500, 600, 700, 800)
+FIRST_FRAME, FRAME_STEP = 9, 10
+
+_WS = {}   # (device, stream, n) -> workspace
+
+
+def _dev64(t, name):
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: the HIP path needs a CUDA/HIP tensor, got {t.device}; there is no CPU fallback")
+    if t.dtype != torch.float64:
+        raise TypeError(f"{name}: expected float64, got {t.dtype}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name}: expected a contiguous tensor")
+    return t.data_ptr()
+
+
+def _workspace(n, device):
+    """Scratch of one dvf_odometry_errors call, cached per length and stream; from the capture's private pool during a
+    HIP-graph capture (as dvf/metrics.py::_workspace)."""
+    m = int(L.lib().dvf_odometry_errors_ws_doubles(n))
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(m, device=device, dtype=torch.float64), m
+    key = (device, L.stream_raw(), n)
+    buf = _WS.get(key)
+    if buf is None:
+        _WS[key] = buf = torch.empty(m, device=device, dtype=torch.float64)
+    return buf, m
+
+
+def n_starts(n):
+    """Number of start frames 9, 19, ... below n."""
+    return len(range(FIRST_FRAME, n, FRAME_STEP))
+
+
+def chain_poses(rel, offsets=None):
+    """Camera-to-world poses [N+S,3,4] fp64 of the relative poses ``rel`` [N,4,4] fp32 on the device: per sequence the
+    identity, then T_k = T_{k-1} @ rel_k.  ``offsets`` (host ints, S+1 of them, offsets[0] = 0, non-decreasing, offsets[S] = N;
+    default one sequence) splits ``rel`` into S <= 32 sequences; sequence s starts at row offsets[s] + s of the result."""
+    L.dev(rel, "rel")
+    if rel.dim() != 3 or tuple(rel.shape[1:]) != (4, 4):
+        raise ValueError(f"chain_poses: rel must be [N,4,4], got {tuple(rel.shape)}")
+    N = rel.shape[0]
+    offsets = [0, N] if offsets is None else [int(o) for o in offsets]
+    S = len(offsets) - 1
+    if S < 1 or offsets[-1] != N:
+        raise ValueError(f"chain_poses: offsets must hold S + 1 >= 2 entries ending at N = {N}, got {offsets}")
+    world = torch.empty(N + S, 3, 4, device=rel.device, dtype=torch.float64)
+    src = rel if N > 0 else torch.empty(16, device=rel.device, dtype=torch.float32)    # an empty tensor has no address
+    L.check(L.lib().dvf_pose_chain(src.data_ptr(), L.int_array(offsets), S, world.data_ptr(), L.stream()), "dvf_pose_chain")
+    return world
+
+
+def sequence_errors(gt, res, summary=None):
+    """KITTI segment errors of the trajectory ``res`` against ``gt``, both [n,3,4] fp64 on the device.  Returns (rows,
+    summary): rows [n_starts(n)*8, 6] = [first, r_err/len, t_err/len, len, speed, valid] (start-major, lengths ascending,
+    all zero where the segment does not end inside the sequence) and summary [4] = [sum t_err/len, sum r_err/len, valid
+    rows, path length of gt].  A ``summary`` passed in has the first three added to it in place (several sequences, one
+    pass)."""
+    _dev64(gt, "gt")
+    _dev64(res, "res")
+    if gt.dim() != 3 or tuple(gt.shape[1:]) != (3, 4) or gt.shape != res.shape or gt.shape[0] < 1:
+        raise ValueError(f"sequence_errors: gt and res must be [n,3,4] of one size, n >= 1, got {tuple(gt.shape)} and "
+                         f"{tuple(res.shape)}")
+    n = gt.shape[0]
+    accumulate = summary is not None
+    if accumulate:
+        _dev64(summary, "summary")
+        if summary.numel() != 4:
+            raise ValueError("sequence_errors: summary must hold 4 doubles")
+    else:
+        summary = torch.empty(4, device=gt.device, dtype=torch.float64)
+    rows = torch.empty(n_starts(n) * len(SEGMENT_LENGTHS), 6, device=gt.device, dtype=torch.float64)
+    ws, m = _workspace(n, gt.device)
+    L.check(L.lib().dvf_odometry_errors(gt.data_ptr(), res.data_ptr(), n, rows.data_ptr() if rows.numel() else None,
+                                        summary.data_ptr(), int(accumulate), ws.data_ptr(), m, L.stream()), "dvf_odometry_errors")
+    return rows, summary
+
+
+def overall(summary):
+    """(mean t_err/len, mean r_err/len) of a summary, on the device; NaN when it counts no row (odometry_eval.overall_error)."""
+    return summary[0] / summary[2], summary[1] / summary[2]

@@ -5,7 +5,11 @@ training hot path, rewritten with vectorised numpy.
   load_poses / trajectory_distances / sequence_errors / overall_error   reference tools/evaluation_tools.py:384-508
                                                              (class kittiEvalOdom, the KITTI devkit metric)
 The reference tool cannot be imported here (caffe, h5py, cv2), so these follow its published algorithm and are
-checked by known-answer tests (tests/test_odometry_eval.py): parity unpinned against the reference itself."""
+checked by known-answer tests (tests/test_odometry_eval.py): parity unpinned against the reference itself.
+
+Run as a script (``python odometry_eval.py --pretrained-pose CKPT --val-root DIR --sequences 09 10``) it evaluates a pose
+checkpoint on the GPU through dvf.cli.validate_odometry / dvf.odometry (csrc/odometry.hip), for which se3_cam2world,
+sequence_errors and overall_error below are the definition; importing this module needs numpy only."""
 import os
 
 import numpy as np
@@ -93,3 +97,48 @@ def overall_error(seq_err):
         return float("nan"), float("nan")
     a = np.asarray(seq_err, dtype=np.float64)
     return float(a[:, 2].mean()), float(a[:, 1].mean())
+
+
+def main(argv=None):
+    """Evaluate a pose checkpoint on KITTI odometry sequences on the GPU (dvf.cli.validate_odometry: the functions above are
+    its definition, restated in csrc/odometry.hip) and print one ``Odometry:`` line per sequence, then the line over all
+    segments of all sequences (the line train.py --val-odometry prints after every epoch).  torch and the GPU are touched
+    only here: importing this module stays numpy-only."""
+    import argparse
+    import torch
+    from PoseExpNet_sfm import PoseExpNet
+    from dataset import odometry_sequences
+    from dvf import cli
+    parser = argparse.ArgumentParser(description="KITTI odometry evaluation of a pose network on MI355X",
+                                     formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    parser.add_argument("--pretrained-pose", required=True, metavar="PATH",
+                        help="PoseExpNet checkpoint (best_odometry_checkpoint.pth.tar / best_vo_checkpoint.pth.tar of train.py)")
+    parser.add_argument("--val-root", required=True, metavar="DIR", help="KITTI odometry tree: sequences/<seq>/image_2, poses/<seq>.txt")
+    parser.add_argument("--sequences", default=["09", "10"], type=str, nargs="+")
+    parser.add_argument("--height", type=int, default=256)
+    parser.add_argument("--width", type=int, default=832)
+    parser.add_argument("-b", "--batch-size", type=int, default=4)
+    parser.add_argument("--pose-convention", choices=list(cli.POSE_CONVENTIONS), default="se3",
+                        help="se3 = (w, u) through the exponential map, what validate() scores; euler = (t, r-euler), what "
+                             "train.py's photometric loss trains the outputs as")
+    parser.add_argument("--output-dir", default=None, metavar="DIR", help="write <seq>.txt, one KITTI pose line per frame")
+    args = parser.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("this build runs on MI355X only: no CUDA/HIP device visible and there is no CPU fallback")
+    device = torch.device("cuda", 0)
+    net = PoseExpNet(nb_ref_imgs=2, output_exp=True)                     # validate()'s call feeds two reference views
+    cli.load_pretrained(net, args.pretrained_pose, strict=False)
+    net.to(device)
+    sequences = odometry_sequences(args.val_root, args.sequences, args.height, args.width)
+    if not sequences:
+        raise SystemExit(f"no sequence of {args.sequences} under {args.val_root}/sequences")
+    metrics = cli.validate_odometry(net, sequences, device, args.batch_size, convention=args.pose_convention,
+                                    output_dir=args.output_dir)
+    for name, m in metrics["per_sequence"].items():
+        print(cli.format_odometry(m, name), flush=True)
+    print(cli.format_odometry(metrics), flush=True)
+    return metrics
+
+
+if __name__ == "__main__":
+    main()

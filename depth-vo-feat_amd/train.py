@@ -8,7 +8,9 @@ instead of nn.DataParallel.  ``validate()`` (odometry L1 against the ground-trut
 train.py:220-247) runs after every epoch when --val-root points at a KITTI-odometry tree (sequences/<seq>/image_2,
 poses/<seq>.txt) and then decides the best checkpoint like the reference; otherwise the best training loss does.
 With --val-depth-root the depth network is validated against ground-truth depth after every epoch as well (Eigen metrics,
-computed on the GPU) and best_depth_checkpoint.pth.tar follows the best abs_rel.
+computed on the GPU) and best_depth_checkpoint.pth.tar follows the best abs_rel.  With --val-odometry (and --val-root) the pose
+network's outputs over each test sequence are chained into a trajectory after every epoch and scored with the KITTI odometry
+errors, on the GPU as well; best_odometry_checkpoint.pth.tar follows the best t_err.
 
     python train.py -b 4 --epochs 2                       # 1 GPU
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py -b 4
@@ -56,11 +58,20 @@ parser.add_argument("--val-depth-root", default=None, metavar="DIR",
                     help="depth validation tree (val.txt, image/<stem>.png|jpg, depth/<stem>.npy in metres, 0 = no measurement): "
                          "after every epoch rank 0 prints the Eigen depth metrics of the depth network against it "
                          "(dvf.cli.validate_depth) and best_depth_checkpoint.pth.tar is saved on the best abs_rel")
+parser.add_argument("--val-odometry", action="store_true",
+                    help="needs --val-root: after every epoch rank 0 also chains the pose network's output over each of "
+                         "--test-sequences into a trajectory and prints its KITTI odometry errors (t_err in %%, r_err in deg / 100 m, "
+                         "computed on the GPU: dvf.cli.validate_odometry); best_odometry_checkpoint.pth.tar is saved on the best t_err")
+parser.add_argument("--pose-convention", choices=list(cli.POSE_CONVENTIONS), default="se3",
+                    help="how --val-odometry reads the pose network's six outputs: se3 = (w, u) through the exponential map, what "
+                         "validate() scores; euler = (t, r-euler), what the photometric loss of this script trains them as")
 cli.add_common_flags(parser)
 
 
 def main():
     args = parser.parse_args()
+    if args.val_odometry and not args.val_root:
+        parser.error("--val-odometry needs --val-root")
     args._rank, args._world, args._device = cli.init_distributed()
     if args.epoch_size:
         args.steps_per_epoch = args.epoch_size
@@ -99,9 +110,16 @@ def main():
         depth_loader = depth_validation_set(args.val_depth_root, args.height, args.width).loader(args.batch_size)
         depth_kwargs = {"depth_val_fn": lambda: cli.validate_depth(disp_net, depth_loader, args._device),
                         "depth_ckpt": ("best_depth_checkpoint.pth.tar", disp_net)}
+    odometry_kwargs = {}
+    if args.val_odometry and args._rank == 0:
+        from dataset import odometry_sequences
+        sequences = odometry_sequences(args.val_root, args.test_sequences, args.height, args.width)
+        odometry_kwargs = {"odometry_val_fn": lambda: cli.validate_odometry(pose_exp_net, sequences, args._device, args.batch_size,
+                                                                           convention=args.pose_convention),
+                           "odometry_ckpt": ("best_odometry_checkpoint.pth.tar", pose_exp_net)}
     cli.run_training(args, [disp_net, pose_exp_net], loss_fn, args.lr, (args.momentum, args.beta), args.weight_decay,
                      terms, [("best_vo_checkpoint.pth.tar", pose_exp_net), ("best_depth_checkpoint.pth.tar", disp_net)],
-                     n_views=max(2, args.nb_ref_imgs), val_fn=val_fn, **depth_kwargs)
+                     n_views=max(2, args.nb_ref_imgs), val_fn=val_fn, **depth_kwargs, **odometry_kwargs)
 
 
 if __name__ == "__main__":

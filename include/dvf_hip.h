@@ -430,6 +430,44 @@ int dvf_depth_metrics(const float *gt, const float *pred, float *out /* [B][12] 
                       int W, int y1, int y2, int x1, int x2, float gt_lo, float gt_hi, float clamp_lo, float clamp_hi,
                       uint32_t flags, void *stream);
 
+/* ---------------------------------------------------------------- odometry evaluation: chained trajectory, KITTI segment errors
+ * The device form of odometry_eval.py's se3_cam2world / sequence_errors / overall_error (reference inference.py:63-70,
+ * tools/evaluation_tools.py:419-508).  All arithmetic is fp64 and these pointers are DEVICE pointers to DOUBLE data unless
+ * stated otherwise.  No allocation, no synchronisation (graph-capturable), no float atomics and a fixed order of every sum:
+ * two runs are bit-identical.
+ *
+ * dvf_pose_chain: rel [N][4][4] fp32 relative poses (the top three rows are read and converted exactly; the fourth is taken
+ *   as 0 0 0 1).  offsets is a HOST array of S+1 ints, read and checked at call time and handed to the kernel by value:
+ *   sequence s owns rel[offsets[s] .. offsets[s+1]) and writes n_s + 1 camera-to-world poses of 12 doubles (a KITTI pose line)
+ *   starting at row offsets[s] + s of world [N+S][3][4]: the identity, then T_k = T_{k-1} * P_k.  An empty sequence writes just
+ *   the identity.  The product is an inclusive scan with (R1,t1)*(R2,t2) = (R1 R2, R1 t2 + t1): one 256-thread block per sequence,
+ *   every thread multiplies a contiguous chunk, the 256 chunk products are scanned through LDS and a second pass applies the
+ *   exclusive prefix.  No re-orthonormalisation (the numpy chain has none); the association differs from the sequential
+ *   chain's, an error of about N * 2^-53 relative.
+ *   DVF_ERR_INVALID_ARG for a null pointer, S outside 1..32, offsets[0] != 0, a decreasing offset or N = offsets[S] >= 2^24.
+ *
+ * dvf_odometry_errors: one sequence, dense trajectories gt and res [n][3][4] (frame i = row i of both).  dist = cumulative
+ *   path length of gt (ws, n doubles: chunk sums, a block scan and a second pass; within 1e-12 relative of the sequential sum).
+ *   For every start frame first = 9, 19, ... < n (nstart of them) and every segment length L = 100, 200 .. 800 m, in that
+ *   order, one row of rows [nstart*8][6]: last = the first index after first with dist[last] > dist[first] + L (binary
+ *   search), e = inv(d_res) * d_gt with d_x = inv(x[first]) * x[last], and the row is
+ *     [first, r_err / L, t_err / L, L, L / (0.1 * (last - first + 1)), 1],   t_err = |e_t|, r_err = acos(clip((tr e_R - 1) / 2));
+ *   a pair without such a last gives an all-zero row.  inv is the inverse of the affine [A|t], (A^-1, -A^-1 t) with A^-1 by
+ *   cofactors: on an orthonormal A it is the rigid inverse (A^T, -A^T t) up to rounding, and on the chained fp32 outputs of a
+ *   network, orthonormal only to ~1e-7, it stays what numpy's general inverse gives.  The angle is the definition's acos form for
+ *   the same reason: atan2(|skew part|, trace - 1) equals it only on an exact rotation and differs from it at first order in
+ *   e_R's departure from one; near zero the acos form resolves angles down to sqrt(2 eps) ~ 2e-8 rad, far below what a segment
+ *   error means.
+ *   summary [4] = [sum t_err/L, sum r_err/L, number of valid rows, path length of gt], the rows added in a fixed order;
+ *   accumulate != 0 adds the first three to what summary holds (the sums over all sequences of a pass, still one
+ *   synchronisation), the fourth is always this sequence's.  n <= 9 has no row: only the summary is written.
+ *   DVF_ERR_INVALID_ARG for n < 1, a null pointer (rows may be null when n <= 9) or ws_doubles below the query. */
+int dvf_pose_chain(const float *rel /* [N][4][4] */, const int *offsets /* HOST, [S+1] */, int S, double *world /* [N+S][3][4] */,
+                   void *stream);
+int64_t dvf_odometry_errors_ws_doubles(int n);
+int dvf_odometry_errors(const double *gt, const double *res /* [n][3][4] each */, int n, double *rows /* [nstart*8][6] */,
+                        double *summary /* [4] */, int accumulate, double *ws, int64_t ws_doubles, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
