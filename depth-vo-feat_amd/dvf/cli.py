@@ -208,8 +208,21 @@ def format_odometry(metrics, name=None):
     return line if name is None else f"{line} seq {name}"
 
 
+TRAJECTORY_FIELDS = ("scale", "ate", "rpe_trans", "rpe_rot", "snippet_ate", "snippet_ate_std", "snippet_re", "snippets")
+
+
+def format_trajectory(metrics, name=None):
+    """The line train.py and odometry_eval.py print after the ``Odometry:`` line of an aligned pass: ``Trajectory: align <mode>
+    scale <c> ATE <m> RPE_t <m> RPE_r <deg> snippet_ATE <mean> +- <std> snippets <count>``, with ``seq <name>`` appended for one
+    sequence of a pass."""
+    line = (f"Trajectory: align {metrics['align']} scale {metrics['scale']:.12g} ATE {metrics['ate']:.12g} "
+            f"RPE_t {metrics['rpe_trans']:.12g} RPE_r {metrics['rpe_rot']:.12g} snippet_ATE {metrics['snippet_ate']:.12g} +- "
+            f"{metrics['snippet_ate_std']:.12g} snippets {metrics['snippets']}")
+    return line if name is None else f"{line} seq {name}"
+
+
 @torch.no_grad()
-def validate_odometry(pose_net, sequences, device, batch_size, convention="se3", output_dir=None, keep=False):
+def validate_odometry(pose_net, sequences, device, batch_size, convention="se3", output_dir=None, keep=False, align=None):
     """Trajectory validation against ground truth: the KITTI odometry errors (tools/evaluation_tools.py:452-508) of the pose
     network's chained trajectory over ``sequences`` = dataset.odometry_sequences(...), as
     {"t_err": percent, "r_err": degrees per 100 m, "segments": count, "per_sequence": {name: the same three + "path_length"}}.
@@ -217,15 +230,28 @@ def validate_odometry(pose_net, sequences, device, batch_size, convention="se3",
     Per sequence, batches of consecutive frame pairs go through the network as in ``validate()`` (eval mode, ``pose_net(later,
     [earlier, earlier])``, output 0); dvf_pose_vec2mat_fwd writes every batch's matrices into one device buffer for all
     sequences, then one dvf.odometry.chain_poses and one sequence_errors per sequence that accumulates into one summary.
-    Everything stays on the device and the pass synchronises once, at its end.  No scale alignment.
+    Everything stays on the device and the pass synchronises once, at its end.  No scale alignment unless ``align`` is given.
 
     ``convention`` names how the six outputs are read, because the reference disagrees with itself: "se3" = (w, u) through the
     se(3) exponential map, what ``validate()`` scores (train.py:229-231); "euler" = (t, r-euler), what train.py's photometric
     loss trains them as (inverse_warp.py:141-157).  ``output_dir``: writes <name>.txt, one KITTI pose line per frame
     (odometry_eval.save_result_poses' format), after the synchronisation.  ``keep``: the result also carries "rel" ([N,4,4]
-    fp32), "world" ([N+S,3,4] fp64) and "offsets" as chain_poses takes and returns them."""
+    fp32), "world" ([N+S,3,4] fp64) and "offsets" as chain_poses takes and returns them.
+
+    ``align``: a mode out of dvf.odometry.ALIGN_MODES ("none" included; None = everything above, unchanged).  Each sequence's
+    chained trajectory is brought onto its ground truth first (dvf.odometry.align: the fit reads the translations only, nothing
+    is re-based) and t_err / r_err / segments are those of the aligned trajectory.  Every per_sequence entry then also carries
+    "align", "scale" (c), "singular_values" (of the cross-covariance: two zeros mean a straight line, no unique rotation), "ate"
+    and "rpe_trans" (m), "rpe_rot" (degrees per frame), and of the 5-frame snippets of inference.py:72-88 "snippet_ate" (mean),
+    "snippet_ate_std" (population), "snippet_re" (mean, degrees) and "snippets" (count).  The top level carries "align", the
+    plain mean over the sequences of scale, ate, rpe_trans, rpe_rot, snippet_ate, snippet_ate_std and snippet_re, and the total
+    "snippets".  Still one synchronisation.  ``output_dir`` also gets <name>_aligned.txt (<name>.txt stays the raw chain) and
+    ``keep`` also returns "aligned", laid out as "world"."""
     from . import lib as L
+    from . import odometry as O
     from .odometry import chain_poses, sequence_errors
+    if align is not None and align not in O.ALIGN_MODES:
+        raise ValueError(f"align must be None or one of {O.ALIGN_MODES}, got {align!r}")
     if convention not in POSE_CONVENTIONS:
         raise ValueError(f"convention must be one of {POSE_CONVENTIONS}, got {convention!r}")
     if not sequences:
@@ -255,12 +281,19 @@ def validate_odometry(pose_net, sequences, device, batch_size, convention="se3",
     rel[:, 3, 3] = 1.0
     world = chain_poses(rel, offsets)
     summary = torch.zeros(4, device=device, dtype=torch.float64)
-    per = []
+    per, extra = [], []
+    aligned = torch.empty_like(world) if align is not None else None
     for s, (_, _, poses) in enumerate(sequences):
         gt = torch.from_numpy(poses).to(device=device, dtype=torch.float64).contiguous()
-        rows, _ = sequence_errors(gt, world[offsets[s] + s:offsets[s + 1] + s + 1], summary)
+        res = world[offsets[s] + s:offsets[s + 1] + s + 1]
+        if align is not None:
+            res, transform = O.align(gt, res, align)
+            aligned[offsets[s] + s:offsets[s + 1] + s + 1] = res
+            # [c, sv (3), ate, rpe_trans, rpe_rot, n, sum ate, sum ate^2, sum re, snippets, 0]
+            extra.append(torch.cat([transform[:1], transform[13:], O.trajectory_errors(gt, res), O.snippet_errors(gt, res)[1]]))
+        rows, _ = sequence_errors(gt, res, summary)
         per.append(torch.stack([rows[:, 2].sum(), rows[:, 1].sum(), rows[:, 5].sum(), summary[3]]))
-    flat = torch.cat([summary[:3]] + per).tolist()                      # the pass's one synchronisation
+    flat = torch.cat([summary[:3]] + per + extra).tolist()              # the pass's one synchronisation
     pose_net.train(was_training)
 
     def metrics(t_sum, r_sum, count):
@@ -272,6 +305,19 @@ def validate_odometry(pose_net, sequences, device, batch_size, convention="se3",
     out["per_sequence"] = {}
     for s, (name, _, _) in enumerate(sequences):
         out["per_sequence"][name] = dict(metrics(*flat[3 + 4 * s:6 + 4 * s]), path_length=flat[6 + 4 * s])
+    if align is not None:
+        deg, nan = 180.0 / math.pi, float("nan")
+        for s, (name, _, _) in enumerate(sequences):
+            c, sv0, sv1, sv2, ate, rpe_t, rpe_r, _, s_ate, s_ate2, s_re, count, _ = flat[3 + 4 * len(sequences) + 13 * s:][:13]
+            mean = s_ate / count if count else nan
+            out["per_sequence"][name].update(
+                align=align, scale=c, singular_values=[sv0, sv1, sv2], ate=ate, rpe_trans=rpe_t, rpe_rot=rpe_r * deg,
+                snippet_ate=mean, snippet_ate_std=math.sqrt(max(s_ate2 / count - mean * mean, 0.0)) if count else nan,
+                snippet_re=s_re / count * deg if count else nan, snippets=int(count))
+        out["align"] = align
+        for k in TRAJECTORY_FIELDS[:-1]:
+            out[k] = sum(m[k] for m in out["per_sequence"].values()) / len(sequences)
+        out["snippets"] = sum(m["snippets"] for m in out["per_sequence"].values())
     if output_dir is not None:
         os.makedirs(output_dir, exist_ok=True)
         host = world.cpu().numpy()
@@ -279,8 +325,16 @@ def validate_odometry(pose_net, sequences, device, batch_size, convention="se3",
             with open(os.path.join(output_dir, f"{name}.txt"), "w") as f:
                 for p in host[offsets[s] + s:offsets[s + 1] + s + 1]:
                     f.write(" ".join(str(v) for v in p.reshape(12)) + "\n")
+        if align is not None:
+            host = aligned.cpu().numpy()
+            for s, (name, _, _) in enumerate(sequences):
+                with open(os.path.join(output_dir, f"{name}_aligned.txt"), "w") as f:
+                    for p in host[offsets[s] + s:offsets[s + 1] + s + 1]:
+                        f.write(" ".join(str(v) for v in p.reshape(12)) + "\n")
     if keep:
         out.update(rel=rel, world=world, offsets=offsets)
+        if align is not None:
+            out["aligned"] = aligned
     return out
 
 
@@ -290,8 +344,8 @@ def run_training(args, nets, loss_fn, lr, betas, weight_decay, term_names, ckpt_
     ``depth_val_fn`` (rank 0, optional): returns the dict of ``validate_depth`` after every epoch; its line is printed and
     ``depth_ckpt`` = (file name, module) is then saved on the best abs_rel instead of on the criterion of the other
     checkpoints, which stays as it is.  ``odometry_val_fn`` (rank 0, optional): returns the dict of ``validate_odometry``
-    after every epoch; its line is printed and ``odometry_ckpt`` = (file name, module), a file of its own, is saved on the
-    best t_err."""
+    after every epoch; its line is printed (and the ``Trajectory:`` line of an aligned pass) and ``odometry_ckpt`` = (file
+    name, module), a file of its own, is saved on the best t_err, the aligned one when the pass aligns."""
     rank, world, device = args._rank, args._world, args._device
     if getattr(args, "deterministic", False):
         from . import conv as _conv
@@ -403,6 +457,8 @@ def run_training(args, nets, loss_fn, lr, betas, weight_decay, term_names, ckpt_
             if odometry_val_fn is not None:
                 odo = odometry_val_fn()
                 print(format_odometry(odo) + " [BEST:{}]".format(odo["t_err"] < best_t_err), flush=True)
+                if "align" in odo:
+                    print(format_trajectory(odo), flush=True)
                 if odo["t_err"] < best_t_err:
                     best_t_err = odo["t_err"]
                     save_best(args.output_dir, [odometry_ckpt])

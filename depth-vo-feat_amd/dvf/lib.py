@@ -106,6 +106,13 @@ SIGNATURES = {
     "dvf_pose_chain": (c_i, [c_fp, c_ip, c_i, c_fp, c_fp]),
     "dvf_odometry_errors_ws_doubles": (c_i64, [c_i]),
     "dvf_odometry_errors": (c_i, [c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_fp, c_i64, c_fp]),
+    "dvf_trajectory_align_ws_doubles": (c_i64, [c_i]),
+    "dvf_trajectory_align": (c_i, [c_fp, c_fp, c_i, c_i, c_fp, c_fp, c_i64, c_fp]),
+    "dvf_trajectory_apply": (c_i, [c_fp, c_fp, c_i, c_i, c_fp, c_fp]),
+    "dvf_trajectory_errors_ws_doubles": (c_i64, [c_i]),
+    "dvf_trajectory_errors": (c_i, [c_fp, c_fp, c_i, c_fp, c_fp, c_i64, c_fp]),
+    "dvf_snippet_errors_ws_doubles": (c_i64, [c_i]),
+    "dvf_snippet_errors": (c_i, [c_fp, c_fp, c_i, c_i, c_fp, c_fp, c_i, c_fp, c_i64, c_fp]),
 }
 
 

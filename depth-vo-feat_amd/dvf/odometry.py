@@ -2,7 +2,10 @@
 the chained camera-to-world trajectory of relative poses and the KITTI segment errors against ground truth, in fp64.
 
 The definition is odometry_eval.py's numpy ``se3_cam2world`` / ``sequence_errors`` / ``overall_error`` for dense trajectories
-(frame i = row i of both).  Nothing here synchronises; every result is ordered on the current stream."""
+(frame i = row i of both).  ``align`` / ``trajectory_errors`` / ``snippet_errors`` (``dvf_trajectory_*`` / ``dvf_snippet_errors``)
+bring the chained trajectory onto the ground truth (scale, 6-DoF, 7-DoF) and score it with ATE, RPE and the scale-aligned
+snippet errors of inference.py:72-88; their definition is odometry_eval.py's trajectory_alignment / apply_alignment /
+trajectory_errors / snippet_errors.  Nothing here synchronises; every result is ordered on the current stream."""
 import torch
 
 from . import lib as L
@@ -10,7 +13,10 @@ from . import lib as L
 SEGMENT_LENGTHS = (100, 200, 300, 400, 500, 600, 700, 800)
 FIRST_FRAME, FRAME_STEP = 9, 10
 
-_WS = {}   # (device, stream, n) -> workspace
+ALIGN_MODES = ("none", "scale", "scale_7dof", "6dof", "7dof")      # index = DVF_ALIGN_* of include/dvf_hip.h
+SNIPPET_LENGTHS = (2, 8)                                           # inclusive
+
+_WS = {}   # (device, stream, n, size query) -> workspace
 
 
 def _dev64(t, name):
@@ -23,13 +29,13 @@ def _dev64(t, name):
     return t.data_ptr()
 
 
-def _workspace(n, device):
-    """Scratch of one dvf_odometry_errors call, cached per length and stream; from the capture's private pool during a
-    HIP-graph capture (as dvf/metrics.py::_workspace)."""
-    m = int(L.lib().dvf_odometry_errors_ws_doubles(n))
+def _workspace(n, device, query="dvf_odometry_errors_ws_doubles"):
+    """Scratch of one call of the entry whose size ``query`` answers, cached per entry, length and stream; from the capture's
+    private pool during a HIP-graph capture (as dvf/metrics.py::_workspace)."""
+    m = int(getattr(L.lib(), query)(n))
     if torch.cuda.is_current_stream_capturing():
         return torch.empty(m, device=device, dtype=torch.float64), m
-    key = (device, L.stream_raw(), n)
+    key = (device, L.stream_raw(), n, query)
     buf = _WS.get(key)
     if buf is None:
         _WS[key] = buf = torch.empty(m, device=device, dtype=torch.float64)
@@ -82,6 +88,69 @@ def sequence_errors(gt, res, summary=None):
     ws, m = _workspace(n, gt.device)
     L.check(L.lib().dvf_odometry_errors(gt.data_ptr(), res.data_ptr(), n, rows.data_ptr() if rows.numel() else None,
                                         summary.data_ptr(), int(accumulate), ws.data_ptr(), m, L.stream()), "dvf_odometry_errors")
+    return rows, summary
+
+
+def _pair(gt, res, what, n_min=1):
+    """The checks every (gt, res) entry shares, before any launch; returns n."""
+    _dev64(gt, "gt")
+    _dev64(res, "res")
+    if gt.dim() != 3 or tuple(gt.shape[1:]) != (3, 4) or gt.shape != res.shape or gt.shape[0] < n_min:
+        raise ValueError(f"{what}: gt and res must be [n,3,4] of one size, n >= {n_min}, got {tuple(gt.shape)} and "
+                         f"{tuple(res.shape)}")
+    return gt.shape[0]
+
+
+def align(gt, res, mode):
+    """The trajectory ``res`` brought onto ``gt`` (both [n,3,4] fp64 on the device, dense, not re-based) by ``mode`` out of
+    ALIGN_MODES: none, scale (least squares about the origin), 6dof (rigid), 7dof (similarity, Umeyama) or scale_7dof (the
+    scale of 7dof alone); the fit reads the translations only.  Returns (aligned [n,3,4], transform [16] = c, R[9], t[3],
+    sv[3]): pose [R_i | t_i] becomes [R R_i | c R t_i + t], sv are the singular values of the cross-covariance (a straight line
+    has sv[1] = sv[2] = 0 and no unique rotation).  Definition: odometry_eval.trajectory_alignment / apply_alignment."""
+    if mode not in ALIGN_MODES:
+        raise ValueError(f"align: mode must be one of {ALIGN_MODES}, got {mode!r}")
+    m = ALIGN_MODES.index(mode)
+    n = _pair(gt, res, f"align ({mode})", 3 if m >= 2 else 1)
+    transform = torch.empty(16, device=gt.device, dtype=torch.float64)
+    aligned = torch.empty_like(res)
+    ws, size = _workspace(n, gt.device, "dvf_trajectory_align_ws_doubles")
+    L.check(L.lib().dvf_trajectory_align(gt.data_ptr(), res.data_ptr(), n, m, transform.data_ptr(), ws.data_ptr(), size, L.stream()),
+            "dvf_trajectory_align")
+    L.check(L.lib().dvf_trajectory_apply(res.data_ptr(), transform.data_ptr(), n, int(m == 0), aligned.data_ptr(), L.stream()),
+            "dvf_trajectory_apply")
+    return aligned, transform
+
+
+def trajectory_errors(gt, res):
+    """[4] = [ate, rpe_trans, rpe_rot (radians), n] of the trajectory ``res`` against ``gt`` as they come (align first), both
+    [n,3,4] fp64 on the device; NaN for the two RPE values when n = 1.  Definition: odometry_eval.trajectory_errors."""
+    n = _pair(gt, res, "trajectory_errors")
+    out = torch.empty(4, device=gt.device, dtype=torch.float64)
+    ws, size = _workspace(n, gt.device, "dvf_trajectory_errors_ws_doubles")
+    L.check(L.lib().dvf_trajectory_errors(gt.data_ptr(), res.data_ptr(), n, out.data_ptr(), ws.data_ptr(), size, L.stream()),
+            "dvf_trajectory_errors")
+    return out
+
+
+def snippet_errors(gt, res, length=5, summary=None):
+    """The scale-aligned snippet errors of inference.py:72-88 over every ``length``-frame window of the trajectories (both
+    [n,3,4] fp64 on the device).  Returns (rows [max(n - length + 1, 0), 2] = [ate, re (radians)], summary [5] = [sum ate,
+    sum ate^2, sum re, rows, 0]).  A ``summary`` passed in has the first four added to it in place.  Definition:
+    odometry_eval.snippet_errors."""
+    if not SNIPPET_LENGTHS[0] <= length <= SNIPPET_LENGTHS[1]:
+        raise ValueError(f"snippet_errors: length must be within {SNIPPET_LENGTHS[0]}..{SNIPPET_LENGTHS[1]}, got {length}")
+    n = _pair(gt, res, "snippet_errors")
+    accumulate = summary is not None
+    if accumulate:
+        _dev64(summary, "summary")
+        if summary.numel() != 5:
+            raise ValueError("snippet_errors: summary must hold 5 doubles")
+    else:
+        summary = torch.empty(5, device=gt.device, dtype=torch.float64)
+    rows = torch.empty(max(n - length + 1, 0), 2, device=gt.device, dtype=torch.float64)
+    ws, size = _workspace(n, gt.device, "dvf_snippet_errors_ws_doubles")
+    L.check(L.lib().dvf_snippet_errors(gt.data_ptr(), res.data_ptr(), n, int(length), rows.data_ptr() if rows.numel() else None,
+                                       summary.data_ptr(), int(accumulate), ws.data_ptr(), size, L.stream()), "dvf_snippet_errors")
     return rows, summary
 
 

@@ -4,12 +4,16 @@ training hot path, rewritten with vectorised numpy.
   save_result_poses / se3_cam2world / compute_pose_error   reference pytorch_version/inference.py:43-88
   load_poses / trajectory_distances / sequence_errors / overall_error   reference tools/evaluation_tools.py:384-508
                                                              (class kittiEvalOdom, the KITTI devkit metric)
+  trajectory_alignment / apply_alignment / trajectory_errors / snippet_errors   alignment of a predicted trajectory to ground
+                                                             truth (scale, 6-DoF, 7-DoF Umeyama), ATE, RPE and compute_pose_error
+                                                             over scale-aligned snippets (the factor inference.py:75 comments out)
 The reference tool cannot be imported here (caffe, h5py, cv2), so these follow its published algorithm and are
 checked by known-answer tests (tests/test_odometry_eval.py): parity unpinned against the reference itself.
 
 Run as a script (``python odometry_eval.py --pretrained-pose CKPT --val-root DIR --sequences 09 10``) it evaluates a pose
 checkpoint on the GPU through dvf.cli.validate_odometry / dvf.odometry (csrc/odometry.hip), for which se3_cam2world,
-sequence_errors and overall_error below are the definition; importing this module needs numpy only."""
+sequence_errors and overall_error below, and with ``--align MODE`` the four alignment functions, are the definition; importing
+this module needs numpy only."""
 import os
 
 import numpy as np
@@ -42,6 +46,112 @@ def compute_pose_error(gt, pred):
     s = np.sqrt((R[:, 0, 1] - R[:, 1, 0]) ** 2 + (R[:, 1, 2] - R[:, 2, 1]) ** 2 + (R[:, 0, 2] - R[:, 2, 0]) ** 2)
     c = np.trace(R, axis1=1, axis2=2) - 1.0
     return ate / n, float(np.arctan2(s, c).sum()) / n
+
+
+ALIGN_MODES = ("none", "scale", "scale_7dof", "6dof", "7dof")
+
+
+def _as44(traj):
+    """[n,4,4] float64 copy of [n,3,4] or [n,4,4] poses, the last row 0 0 0 1."""
+    a = np.asarray(traj, dtype=np.float64)
+    out = np.tile(np.eye(4), (a.shape[0], 1, 1))
+    out[:, :3, :4] = a[:, :3, :4]
+    return out
+
+
+def trajectory_alignment(gt, res, mode):
+    """The transform (c, R, t, sv) that brings the trajectory ``res`` onto ``gt`` (both [n,3,4] or [n,4,4], dense: frame i is
+    row i of both), fitted on the translation columns x_i of res and y_i of gt alone.  Nothing is re-based: KITTI ground truth
+    and se3_cam2world both start at the identity; other inputs must be re-based by the caller.
+
+      none        c = 1, R = I, t = 0
+      scale       c = sum y.x / sum x.x about the origin (the factor inference.py:75 comments out), 1 when the denominator is 0
+      7dof        Umeyama: Sigma = 1/n sum (y - my)(x - mx)^T = U D V^T, S = diag(1, 1, sign(det U det V)), R = U S V^T (a proper
+                  rotation, never a reflection), c = tr(D S) / var_x (1 when var_x is 0), t = my - c R mx
+      6dof        the same with c = 1
+      scale_7dof  c of 7dof, R = I, t = 0
+
+    sv holds the singular values of Sigma (zeros for none / scale): a straight line has sv[1] = sv[2] = 0 and no unique
+    rotation.  The centred sums are a second pass over the data after the means, so a large common offset costs nothing."""
+    if mode not in ALIGN_MODES:
+        raise ValueError(f"mode must be one of {ALIGN_MODES}, got {mode!r}")
+    x = np.asarray(res, dtype=np.float64)[:, :3, 3]
+    y = np.asarray(gt, dtype=np.float64)[:, :3, 3]
+    if x.shape != y.shape or x.shape[0] < 1:
+        raise ValueError(f"gt and res must hold the same n >= 1 poses, got {y.shape[0]} and {x.shape[0]}")
+    c, R, t, sv = 1.0, np.eye(3), np.zeros(3), np.zeros(3)
+    if mode == "none":
+        return c, R, t, sv
+    if mode == "scale":
+        den = float((x * x).sum())
+        return (float((y * x).sum()) / den if den != 0.0 else 1.0), R, t, sv
+    n = x.shape[0]
+    if n < 3:
+        raise ValueError(f"mode {mode!r} needs n >= 3 poses, got {n}")
+    mx, my = x.mean(0), y.mean(0)
+    xc, yc = x - mx, y - my
+    var = float((xc * xc).sum()) / n
+    U, sv, Vt = np.linalg.svd(yc.T @ xc / n)
+    S = np.diag([1.0, 1.0, -1.0 if np.linalg.det(U) * np.linalg.det(Vt) < 0 else 1.0])
+    rot = U @ S @ Vt
+    c7 = float(np.trace(np.diag(sv) @ S)) / var if var != 0.0 else 1.0
+    if mode == "scale_7dof":
+        return c7, R, t, sv
+    c = c7 if mode == "7dof" else 1.0
+    return c, rot, my - c * rot @ mx, sv
+
+
+def apply_alignment(res, c, R, t):
+    """Every pose [R_i | t_i] of ``res`` mapped to [R R_i | c R t_i + t]; the result has the shape of ``res``."""
+    out = np.array(res, dtype=np.float64)
+    R, t = np.asarray(R, dtype=np.float64), np.asarray(t, dtype=np.float64)
+    out[:, :3, :3] = R @ out[:, :3, :3]
+    out[:, :3, 3] = c * (out[:, :3, 3] @ R.T) + t
+    return out
+
+
+def _angles(R):
+    """atan2(|skew part|, trace - 1) of [m,3,3]: the angle form of compute_pose_error, exact down to zero (arccos of the
+    trace loses eight digits at 1e-4 rad)."""
+    s = np.sqrt((R[:, 0, 1] - R[:, 1, 0]) ** 2 + (R[:, 1, 2] - R[:, 2, 1]) ** 2 + (R[:, 0, 2] - R[:, 2, 0]) ** 2)
+    return np.arctan2(s, np.trace(R, axis1=1, axis2=2) - 1.0)
+
+
+def trajectory_errors(gt, res):
+    """(ate, rpe_trans, rpe_rot) of dense trajectories, as they come (align first): ate = sqrt(mean |y_i - x_i|^2) over the
+    translations; for every consecutive pair E = inv(inv(gt_i) gt_{i+1}) (inv(res_i) res_{i+1}) with the affine inverse,
+    rpe_trans the mean of |E_t| and rpe_rot the mean of the atan2 angle of E_R (radians).  Both RPE values are NaN for n < 2."""
+    g, r = _as44(gt), _as44(res)
+    if g.shape != r.shape or g.shape[0] < 1:
+        raise ValueError(f"gt and res must hold the same n >= 1 poses, got {g.shape[0]} and {r.shape[0]}")
+    ate = float(np.sqrt(((g[:, :3, 3] - r[:, :3, 3]) ** 2).sum(1).mean()))
+    if g.shape[0] < 2:
+        return ate, float("nan"), float("nan")
+    d_gt = np.linalg.inv(g[:-1]) @ g[1:]
+    d_res = np.linalg.inv(r[:-1]) @ r[1:]
+    E = np.linalg.inv(d_gt) @ d_res
+    return ate, float(np.linalg.norm(E[:, :3, 3], axis=1).mean()), float(_angles(E[:, :3, :3]).mean())
+
+
+def snippet_errors(gt, res, length=5):
+    """[n - length + 1, 2] rows [ate, re] of every ``length``-frame snippet (start frames 0 .. n - length): both snippets are
+    re-based to their first frame, the predicted translations are multiplied by s = sum g.p / sum p.p over the snippet (1 when
+    the denominator is 0; the factor of inference.py:75), and the row is compute_pose_error of the two.  [0, 2] when
+    n < length; 2 <= length <= 8."""
+    if not 2 <= length <= 8:
+        raise ValueError(f"length must be within 2..8, got {length}")
+    g, r = _as44(gt), _as44(res)
+    if g.shape != r.shape:
+        raise ValueError(f"gt and res must hold the same number of poses, got {g.shape[0]} and {r.shape[0]}")
+    rows = np.zeros((max(g.shape[0] - length + 1, 0), 2))
+    for i in range(rows.shape[0]):
+        a = np.linalg.inv(g[i]) @ g[i:i + length]
+        p = np.linalg.inv(r[i]) @ r[i:i + length]
+        den = float((p[:, :3, 3] * p[:, :3, 3]).sum())
+        s = float((a[:, :3, 3] * p[:, :3, 3]).sum()) / den if den != 0.0 else 1.0
+        p[:, :3, 3] *= s
+        rows[i] = compute_pose_error(a[:, :3], p[:, :3])
+    return rows
 
 
 def load_poses(file_name):
@@ -122,6 +232,11 @@ def main(argv=None):
                         help="se3 = (w, u) through the exponential map, what validate() scores; euler = (t, r-euler), what "
                              "train.py's photometric loss trains the outputs as")
     parser.add_argument("--output-dir", default=None, metavar="DIR", help="write <seq>.txt, one KITTI pose line per frame")
+    parser.add_argument("--align", choices=list(ALIGN_MODES), default=None, metavar="MODE",
+                        help="bring every chained trajectory onto its ground truth first, by one of " + ", ".join(ALIGN_MODES) +
+                             " (scale: least squares about the origin; 6dof: rigid; 7dof: similarity, Umeyama; scale_7dof: the "
+                             "scale of 7dof alone): the Odometry line is then that of the aligned trajectory, a Trajectory line "
+                             "with ATE, RPE and the 5-frame-snippet ATE follows it, and --output-dir also gets <seq>_aligned.txt")
     args = parser.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("this build runs on MI355X only: no CUDA/HIP device visible and there is no CPU fallback")
@@ -133,10 +248,14 @@ def main(argv=None):
     if not sequences:
         raise SystemExit(f"no sequence of {args.sequences} under {args.val_root}/sequences")
     metrics = cli.validate_odometry(net, sequences, device, args.batch_size, convention=args.pose_convention,
-                                    output_dir=args.output_dir)
+                                    output_dir=args.output_dir, align=args.align)
     for name, m in metrics["per_sequence"].items():
         print(cli.format_odometry(m, name), flush=True)
+        if args.align is not None:
+            print(cli.format_trajectory(m, name), flush=True)
     print(cli.format_odometry(metrics), flush=True)
+    if args.align is not None:
+        print(cli.format_trajectory(metrics), flush=True)
     return metrics
 
 

@@ -10,7 +10,9 @@ poses/<seq>.txt) and then decides the best checkpoint like the reference; otherw
 With --val-depth-root the depth network is validated against ground-truth depth after every epoch as well (Eigen metrics,
 computed on the GPU) and best_depth_checkpoint.pth.tar follows the best abs_rel.  With --val-odometry (and --val-root) the pose
 network's outputs over each test sequence are chained into a trajectory after every epoch and scored with the KITTI odometry
-errors, on the GPU as well; best_odometry_checkpoint.pth.tar follows the best t_err.
+errors, on the GPU as well; best_odometry_checkpoint.pth.tar follows the best t_err.  --val-odometry-align MODE first brings
+every trajectory onto its ground truth (scale, 6dof, 7dof: a monocular network's scale is arbitrary), so that t_err is the
+aligned one, and prints ATE, RPE and the 5-frame-snippet ATE in a Trajectory line.
 
     python train.py -b 4 --epochs 2                       # 1 GPU
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py -b 4
@@ -26,6 +28,7 @@ import torch  # noqa: E402
 from DispNetS import DispNetS  # noqa: E402
 from PoseExpNet_sfm import PoseExpNet  # noqa: E402
 from dvf import cli  # noqa: E402
+from dvf.odometry import ALIGN_MODES  # noqa: E402
 from dvf.steps import train_sfm_losses  # noqa: E402
 
 parser = argparse.ArgumentParser(description="Unsupervised depth + pose training (sfm loss form) on MI355X",
@@ -65,6 +68,11 @@ parser.add_argument("--val-odometry", action="store_true",
 parser.add_argument("--pose-convention", choices=list(cli.POSE_CONVENTIONS), default="se3",
                     help="how --val-odometry reads the pose network's six outputs: se3 = (w, u) through the exponential map, what "
                          "validate() scores; euler = (t, r-euler), what the photometric loss of this script trains them as")
+parser.add_argument("--val-odometry-align", choices=list(ALIGN_MODES), default=None, metavar="MODE",
+                    help="needs --val-odometry: every chained trajectory is first brought onto its ground truth by one of " +
+                         ", ".join(ALIGN_MODES) + " (a monocular network's scale is arbitrary: scale or 7dof removes it); "
+                         "best_odometry_checkpoint.pth.tar then follows the aligned t_err, and a Trajectory line (ATE, RPE, "
+                         "5-frame-snippet ATE) is printed after the Odometry line")
 cli.add_common_flags(parser)
 
 
@@ -72,6 +80,8 @@ def main():
     args = parser.parse_args()
     if args.val_odometry and not args.val_root:
         parser.error("--val-odometry needs --val-root")
+    if args.val_odometry_align is not None and not args.val_odometry:
+        parser.error("--val-odometry-align needs --val-odometry")
     args._rank, args._world, args._device = cli.init_distributed()
     if args.epoch_size:
         args.steps_per_epoch = args.epoch_size
@@ -115,7 +125,8 @@ def main():
         from dataset import odometry_sequences
         sequences = odometry_sequences(args.val_root, args.test_sequences, args.height, args.width)
         odometry_kwargs = {"odometry_val_fn": lambda: cli.validate_odometry(pose_exp_net, sequences, args._device, args.batch_size,
-                                                                           convention=args.pose_convention),
+                                                                           convention=args.pose_convention,
+                                                                           align=args.val_odometry_align),
                            "odometry_ckpt": ("best_odometry_checkpoint.pth.tar", pose_exp_net)}
     cli.run_training(args, [disp_net, pose_exp_net], loss_fn, args.lr, (args.momentum, args.beta), args.weight_decay,
                      terms, [("best_vo_checkpoint.pth.tar", pose_exp_net), ("best_depth_checkpoint.pth.tar", disp_net)],

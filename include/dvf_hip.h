@@ -468,6 +468,61 @@ int64_t dvf_odometry_errors_ws_doubles(int n);
 int dvf_odometry_errors(const double *gt, const double *res /* [n][3][4] each */, int n, double *rows /* [nstart*8][6] */,
                         double *summary /* [4] */, int accumulate, double *ws, int64_t ws_doubles, void *stream);
 
+/* Alignment of a trajectory to ground truth and the errors of the aligned trajectory: the device form of odometry_eval.py's
+ * trajectory_alignment / apply_alignment / trajectory_errors / snippet_errors (reference inference.py:72-88, compute_pose_error,
+ * with the scale factor that its line 75 comments out).  Same rules as above; gt and res are dense [n][3][4] trajectories, frame
+ * i = row i of both, nothing is re-based.  Sums over the frames are per-block partials (256 frames a block, a fixed LDS tree)
+ * in ws, added in block order.  Every entry: DVF_ERR_INVALID_ARG for n < 1 or n >= 2^24, a null pointer, or ws_doubles below the
+ * entry's query.
+ *
+ * dvf_trajectory_align: fits, on the translation columns x_i of res and y_i of gt alone, the transform record
+ *   transform [16] = c, R[9] (row-major), t[3], sv[3]   for mode
+ *     DVF_ALIGN_NONE        c = 1, R = I, t = 0
+ *     DVF_ALIGN_SCALE       c = sum y.x / sum x.x about the origin, uncentred (1 when the denominator is exactly 0), R = I, t = 0
+ *     DVF_ALIGN_7DOF        Umeyama: Sigma = 1/n sum (y - my)(x - mx)^T = U D V^T, S = diag(1, 1, sign(det U det V)),
+ *                           R = U S V^T, c = tr(D S) / var_x with var_x = 1/n sum |x - mx|^2 (1 when it is exactly 0),
+ *                           t = my - c R mx
+ *     DVF_ALIGN_6DOF        the same with c = 1
+ *     DVF_ALIGN_SCALE_7DOF  c of 7DOF, R = I, t = 0
+ *   sv = the singular values of Sigma, descending (zeros for NONE / SCALE): a straight line has sv[1] = sv[2] = 0 and no unique
+ *   rotation.  The centred sums are a second pass over the data after the means (a first pass leaves sum x, sum y, sum y.x,
+ *   sum x.x), so a common offset of 1e6 m costs nothing.  One thread solves the 3x3 problem by one-sided Jacobi rotations of
+ *   Sigma's columns (nothing is squared) and builds R from the two leading singular pairs and their cross products: it is a
+ *   proper rotation, orthonormal with determinant +1 to rounding, for every input, rank-deficient ones included (rank 1: an
+ *   optimal rotation among the many; Sigma = 0: the identity).  The last three modes need n >= 3; an unknown mode is an error.
+ *
+ * dvf_trajectory_apply: out_i = [R R_i | c R t_i + t] for every pose of res, one thread per pose; copy != 0 copies res
+ *   unchanged and does not read transform (mode NONE).  out may not overlap res.
+ *
+ * dvf_trajectory_errors: out [4] = [ate, rpe_trans, rpe_rot, n]: ate = sqrt(1/n sum |y_i - x_i|^2); for the n - 1 consecutive
+ *   pairs E = inv(inv(gt_i) gt_{i+1}) * (inv(res_i) res_{i+1}), rpe_trans = mean |E_t|, rpe_rot = mean atan2(s, tr E_R - 1) in
+ *   radians, s the norm of the three off-diagonal differences of E_R (compute_pose_error's angle, inference.py:82-86: exact down
+ *   to zero, where the acos of the trace loses eight digits at 1e-4 rad).  inv is the affine inverse of dvf_odometry_errors.
+ *   n = 1: both RPE values are NaN.
+ *
+ * dvf_snippet_errors: for every start frame i = 0 .. n - length (nrows = n - length + 1 of them, none when n < length) both
+ *   length-frame snippets are re-based to their first frame, inv(first) * each, the predicted translations are multiplied by
+ *   s = sum g.p / sum p.p over the snippet (1 when the denominator is exactly 0) and rows [nrows][2] gets compute_pose_error's
+ *   pair: ate = |all translation differences| / length, re = (sum of the angles of R_g inv(R_p)) / length, the angle as above.
+ *   summary [5] = [sum ate, sum ate^2, sum re, nrows, 0], the rows added in a fixed order; accumulate != 0 adds the first four
+ *   to what summary holds.  length outside 2..8 is an error; rows may be null when n < length. */
+#define DVF_ALIGN_NONE 0
+#define DVF_ALIGN_SCALE 1
+#define DVF_ALIGN_SCALE_7DOF 2
+#define DVF_ALIGN_6DOF 3
+#define DVF_ALIGN_7DOF 4
+int64_t dvf_trajectory_align_ws_doubles(int n);
+int dvf_trajectory_align(const double *gt, const double *res /* [n][3][4] each */, int n, int mode, double *transform /* [16] */,
+                         double *ws, int64_t ws_doubles, void *stream);
+int dvf_trajectory_apply(const double *res /* [n][3][4] */, const double *transform /* [16] */, int n, int copy,
+                         double *out /* [n][3][4] */, void *stream);
+int64_t dvf_trajectory_errors_ws_doubles(int n);
+int dvf_trajectory_errors(const double *gt, const double *res /* [n][3][4] each */, int n, double *out /* [4] */, double *ws,
+                          int64_t ws_doubles, void *stream);
+int64_t dvf_snippet_errors_ws_doubles(int n);
+int dvf_snippet_errors(const double *gt, const double *res /* [n][3][4] each */, int n, int length, double *rows /* [nrows][2] */,
+                       double *summary /* [5] */, int accumulate, double *ws, int64_t ws_doubles, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
