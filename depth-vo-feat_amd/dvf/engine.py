@@ -10,7 +10,9 @@ checkpoints and user code see ordinary tensors, while
   * the all-reduce works on contiguous slices of it (no bucket copies),
   * Adam is one kernel launch per contiguous run of parameters that received a gradient.
 Reference semantics kept: ``torch.optim.Adam`` as configured at train.py:150-156 / unsupervise.py:241,
-including "parameters without a gradient are skipped".
+including "parameters without a gradient are skipped".  One difference: the step counter is global (one device counter for the
+arena), so a parameter whose first gradient arrives in step k > 1 is bias-corrected with t = k, where torch.optim.Adam would start
+that parameter's own counter at 1; no step body of this project does that.
 """
 import torch
 import torch.distributed as dist
