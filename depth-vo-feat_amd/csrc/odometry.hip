@@ -216,53 +216,6 @@ __global__ __launch_bounds__(NT) void rows_kernel(const double *gt, const double
     row[5] = 1.0;
 }
 
-// summary = [sum t_err/L, sum r_err/L, rows, path length].  With no row (n <= 9) no dist exists: thread 0 walks the few steps.
-__global__ __launch_bounds__(NT) void summary_kernel(const double *gt, const double *rows, const double *dist, int n, int nrows,
-                                                     int accumulate, double *summary) {
-    __shared__ double s[3][NT];
-    const int tid = threadIdx.x;
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int i = tid; i < nrows; i += NT) {
-        const double *row = rows + (int64_t)i * ROW;
-        acc[0] += row[2];
-        acc[1] += row[1];
-        acc[2] += row[5];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) s[c][tid] = acc[c];
-    __syncthreads();
-    for (int d = NT / 2; d > 0; d >>= 1) {
-        if (tid < d) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) s[c][tid] += s[c][tid + d];
-        }
-        __syncthreads();
-    }
-    if (tid != 0) return;
-    double path = 0.0;
-    if (nrows > 0) path = dist[n - 1];
-    else
-        for (int i = 1; i < n; ++i) path += step_norm(gt, i);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) summary[c] = accumulate ? summary[c] + s[c][0] : s[c][0];
-    summary[3] = path;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// Trajectory alignment and the errors of an aligned trajectory (odometry_eval.py's trajectory_alignment / apply_alignment /
-// trajectory_errors / snippet_errors; reference inference.py:72-88 with the scale factor of :75).  The same rules: fp64, no
-// atomics, every sum in a fixed order.  Sums over the frames are block partials (one 256-thread block per 256 frames, a fixed
-// LDS tree) left in scratch, then added in block order:
-//   align_sums_kernel      per block sum x (3), sum y (3), sum y.x, sum x.x of the translations x of res and y of gt
-//   align_centred_kernel   the means from those partials in block order, then per block sum |x - mx|^2 and the nine entries of
-//                          sum (y - my)(x - mx)^T: a second pass over the data, so a common offset of 1e6 m costs nothing
-//   align_solve_kernel     one block adds the partials in block order, thread 0 solves the 3x3 problem and writes the record
-//   apply_kernel           one thread per pose: [R R_i | c R t_i + t]
-//   pair_errors_kernel / pair_finish_kernel        ATE and RPE
-//   snippet_kernel / snippet_finish_kernel         one thread per start frame, the snippet's translations in registers
-constexpr int ALIGN_NONE = 0, ALIGN_SCALE = 1, ALIGN_SCALE_7DOF = 2, ALIGN_6DOF = 3, ALIGN_7DOF = 4;
-constexpr int SUMS = 8, CENTRED = 10, MAX_SNIPPET = 8;
-
 // the block's sum of acc[k] in a fixed tree; thread 0 returns with the totals in acc
 template <int K>
 __device__ __forceinline__ void block_sum(double (&acc)[K], double (*s)[NT]) {
@@ -281,6 +234,59 @@ __device__ __forceinline__ void block_sum(double (&acc)[K], double (*s)[NT]) {
     for (int k = 0; k < K; ++k) acc[k] = s[k][0];
 }
 
+// thread 0 stores the block's K totals (block_sum's result) at the block's slot of part
+template <int K>
+__device__ __forceinline__ void store_block_totals(const double (&acc)[K], double *part) {
+    if (threadIdx.x != 0) return;
+#pragma unroll
+    for (int k = 0; k < K; ++k) part[(int64_t)blockIdx.x * K + k] = acc[k];
+}
+
+// part[k] + part[stride + k] + ... over nb blocks, in block order
+__device__ __forceinline__ double sum_in_block_order(const double *part, int nb, int stride, int k) {
+    double m = 0.0;
+    for (int b = 0; b < nb; ++b) m += part[(int64_t)b * stride + k];
+    return m;
+}
+
+// summary = [sum t_err/L, sum r_err/L, rows, path length].  With no row (n <= 9) no dist exists: thread 0 walks the few steps.
+__global__ __launch_bounds__(NT) void summary_kernel(const double *gt, const double *rows, const double *dist, int n, int nrows,
+                                                     int accumulate, double *summary) {
+    __shared__ double s[3][NT];
+    const int tid = threadIdx.x;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int i = tid; i < nrows; i += NT) {
+        const double *row = rows + (int64_t)i * ROW;
+        acc[0] += row[2];
+        acc[1] += row[1];
+        acc[2] += row[5];
+    }
+    block_sum<3>(acc, s);
+    if (tid != 0) return;
+    double path = 0.0;
+    if (nrows > 0) path = dist[n - 1];
+    else
+        for (int i = 1; i < n; ++i) path += step_norm(gt, i);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) summary[c] = accumulate ? summary[c] + acc[c] : acc[c];
+    summary[3] = path;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Trajectory alignment and the errors of an aligned trajectory (odometry_eval.py's trajectory_alignment / apply_alignment /
+// trajectory_errors / snippet_errors; reference inference.py:72-88 with the scale factor of :75).  The same rules: fp64, no
+// atomics, every sum in a fixed order.  Sums over the frames are block partials (one 256-thread block per 256 frames, a fixed
+// LDS tree) left in scratch, then added in block order:
+//   align_sums_kernel      per block sum x (3), sum y (3), sum y.x, sum x.x of the translations x of res and y of gt
+//   align_centred_kernel   the means from those partials in block order, then per block sum |x - mx|^2 and the nine entries of
+//                          sum (y - my)(x - mx)^T: a second pass over the data, so a common offset of 1e6 m costs nothing
+//   align_solve_kernel     one block adds the partials in block order, thread 0 solves the 3x3 problem and writes the record
+//   apply_kernel           one thread per pose: [R R_i | c R t_i + t]
+//   pair_errors_kernel / pair_finish_kernel        ATE and RPE
+//   snippet_kernel / snippet_finish_kernel         one thread per start frame, the snippet's translations in registers
+constexpr int ALIGN_NONE = 0, ALIGN_SCALE = 1, ALIGN_SCALE_7DOF = 2, ALIGN_6DOF = 3, ALIGN_7DOF = 4;
+constexpr int SUMS = 8, CENTRED = 10, MAX_SNIPPET = 8;
+
 __global__ __launch_bounds__(NT) void align_sums_kernel(const double *gt, const double *res, int n, double *part) {
     __shared__ double s[SUMS][NT];
     const int i = blockIdx.x * NT + threadIdx.x;
@@ -297,10 +303,7 @@ __global__ __launch_bounds__(NT) void align_sums_kernel(const double *gt, const 
         acc[7] = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
     }
     block_sum<SUMS>(acc, s);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < SUMS; ++k) part[(int64_t)blockIdx.x * SUMS + k] = acc[k];
-    }
+    store_block_totals<SUMS>(acc, part);
 }
 
 __global__ __launch_bounds__(NT) void align_centred_kernel(const double *gt, const double *res, int n, int nb, const double *part,
@@ -308,9 +311,7 @@ __global__ __launch_bounds__(NT) void align_centred_kernel(const double *gt, con
     __shared__ double s[CENTRED][NT];
     __shared__ double mean[6];
     if (threadIdx.x < 6) {                                             // mx, my: the partials in block order
-        double m = 0.0;
-        for (int b = 0; b < nb; ++b) m += part[(int64_t)b * SUMS + threadIdx.x];
-        mean[threadIdx.x] = m / (double)n;
+        mean[threadIdx.x] = sum_in_block_order(part, nb, SUMS, threadIdx.x) / (double)n;
     }
     __syncthreads();
     const int i = blockIdx.x * NT + threadIdx.x;
@@ -327,10 +328,7 @@ __global__ __launch_bounds__(NT) void align_centred_kernel(const double *gt, con
         }
     }
     block_sum<CENTRED>(acc, s);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < CENTRED; ++k) cpart[(int64_t)blockIdx.x * CENTRED + k] = acc[k];
-    }
+    store_block_totals<CENTRED>(acc, cpart);
 }
 
 __device__ __forceinline__ void cross3(const double *a, const double *b, double *o) {
@@ -449,10 +447,8 @@ __global__ __launch_bounds__(64) void align_solve_kernel(const double *part, con
     const int tid = threadIdx.x;
     if (mode != ALIGN_NONE && tid < SUMS + CENTRED) {
         double m = 0.0;
-        if (tid < SUMS)
-            for (int b = 0; b < nb; ++b) m += part[(int64_t)b * SUMS + tid];
-        else if (mode != ALIGN_SCALE)
-            for (int b = 0; b < nb; ++b) m += cpart[(int64_t)b * CENTRED + (tid - SUMS)];
+        if (tid < SUMS) m = sum_in_block_order(part, nb, SUMS, tid);
+        else if (mode != ALIGN_SCALE) m = sum_in_block_order(cpart, nb, CENTRED, tid - SUMS);
         tot[tid] = m;
     }
     __syncthreads();
@@ -531,21 +527,14 @@ __global__ __launch_bounds__(NT) void pair_errors_kernel(const double *gt, const
         }
     }
     block_sum<3>(acc, s);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) part[(int64_t)blockIdx.x * 3 + k] = acc[k];
-    }
+    store_block_totals<3>(acc, part);
 }
 
 // out [4] = [ate, rpe_trans, rpe_rot, n]
 __global__ __launch_bounds__(64) void pair_finish_kernel(const double *part, int n, int nb, double *out) {
     __shared__ double tot[3];
     const int tid = threadIdx.x;
-    if (tid < 3) {
-        double m = 0.0;
-        for (int b = 0; b < nb; ++b) m += part[(int64_t)b * 3 + tid];
-        tot[tid] = m;
-    }
+    if (tid < 3) tot[tid] = sum_in_block_order(part, nb, 3, tid);
     __syncthreads();
     if (tid != 0) return;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
@@ -604,18 +593,14 @@ __global__ __launch_bounds__(NT) void snippet_kernel(const double *gt, const dou
         acc[2] = re;
     }
     block_sum<3>(acc, s);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) part[(int64_t)blockIdx.x * 3 + k] = acc[k];
-    }
+    store_block_totals<3>(acc, part);
 }
 
 // summary [5] = [sum ate, sum ate^2, sum re, rows, 0]
 __global__ __launch_bounds__(64) void snippet_finish_kernel(const double *part, int nrows, int nb, int accumulate, double *summary) {
     const int tid = threadIdx.x;
     if (tid < 3) {
-        double m = 0.0;
-        for (int b = 0; b < nb; ++b) m += part[(int64_t)b * 3 + tid];
+        const double m = sum_in_block_order(part, nb, 3, tid);
         summary[tid] = accumulate ? summary[tid] + m : m;
     } else if (tid == 3) {
         summary[3] = accumulate ? summary[3] + (double)nrows : (double)nrows;

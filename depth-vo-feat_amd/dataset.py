@@ -80,7 +80,7 @@ class pose_framework_KITTI(data.Dataset):
 
 
 def odometry_sequences(root, sequence_set, img_height, img_width):
-    """The sequences of ``sequence_set`` under ``root`` one by one, for ``dvf.cli.validate_odometry``: a list of (name,
+    """The sequences of ``sequence_set`` under ``root`` one by one, for ``dvf.validation.validate_odometry``: a list of (name,
     pairs, poses) in directory order.  ``pairs`` is ``pose_framework_KITTI(root, [name], shuffle=False)``: its sample i is
     the frame pair (i, i + 1) in ``validate()``'s layout, in frame order; ``poses`` is the ground truth of ``poses/<name>.txt``
     as [n,3,4] float64 (``read_scene_data`` keeps float32, enough for a relative pose but not for a trajectory of kilometres),
@@ -99,7 +99,7 @@ def odometry_sequences(root, sequence_set, img_height, img_width):
 
 
 class DepthValidationSet(data.Dataset):
-    """Frames with ground-truth depth for ``dvf.cli.validate_depth``.  Layout: ``root/val.txt`` holds one stem per line,
+    """Frames with ground-truth depth for ``dvf.validation.validate_depth``.  Layout: ``root/val.txt`` holds one stem per line,
     ``root/image/<stem>.png|jpg`` the frame and ``root/depth/<stem>.npy`` a float32 [Hg,Wg] map in metres with 0 for no
     measurement (a projected LiDAR sweep).  A sample is (frame [3,img_height,img_width] float32, depth [Hg,Wg] float32): the
     frame goes through the same ``imread`` / ``imresize`` and keeps the value range (0..255) that ``un_dataset.dataset``

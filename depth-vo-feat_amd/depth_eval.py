@@ -7,7 +7,7 @@ answers in tests/test_depth_eval.py.  ``evaluate`` applies the usual KITTI proto
 depth cap, optional Garg crop, optional median scaling.
 
 Run as a script (``python depth_eval.py --pretrained-disp CKPT --val-depth-root DIR``) it evaluates a checkpoint on the GPU
-through dvf.cli.validate_depth / dvf.metrics.depth_metrics instead.  The two differ in one documented place: ``evaluate``
+through dvf.validation.validate_depth / dvf.metrics.depth_metrics instead.  The two differ in one documented place: ``evaluate``
 uses numpy's median, the MEAN OF THE TWO middle elements for an even count, while the device path takes torch.median's lower
 median as the reference's training-side compute_errors does (loss_functions_sfm.py:104); the mean-of-two form is not
 reproduced on the device.  The device path also clamps once, before scaling, unless asked to reclamp."""
@@ -25,10 +25,17 @@ def compute_errors(gt, pred):
     return abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3
 
 
+def garg_rect(h, w):
+    """(y1, y2, x1, x2) of the crop of Garg et al. (ECCV16) used to reproduce Eigen's results: the int(...) constants of
+    loss_functions_sfm.py:92-93.  dvf.metrics.depth_metrics takes its default rectangle from here."""
+    return int(0.40810811 * h), int(0.99189189 * h), int(0.03594771 * w), int(0.96405229 * w)
+
+
 def garg_crop_mask(h, w):
-    """Crop of Garg et al. (ECCV16) used to reproduce Eigen's results (same constants as loss_functions_sfm.py:93-96)."""
+    """garg_rect as a boolean [h, w] mask."""
+    y1, y2, x1, x2 = garg_rect(h, w)
     m = np.zeros((h, w), dtype=bool)
-    m[int(0.40810811 * h):int(0.99189189 * h), int(0.03594771 * w):int(0.96405229 * w)] = True
+    m[y1:y2, x1:x2] = True
     return m
 
 
@@ -55,7 +62,7 @@ def main(argv=None):
     import torch
     from DispNetS import DispNetS
     from dataset import depth_validation_set
-    from dvf import cli
+    from dvf import cli, validation
     parser = argparse.ArgumentParser(description="Depth evaluation against ground truth on MI355X",
                                      formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     parser.add_argument("--pretrained-disp", required=True, metavar="PATH", help="DispNetS checkpoint (best_depth_checkpoint.pth.tar)")
@@ -67,15 +74,14 @@ def main(argv=None):
     parser.add_argument("--no-crop", action="store_true", help="all pixels instead of the Garg crop")
     parser.add_argument("--no-median-scaling", action="store_true", help="compare the prediction as it is")
     args = parser.parse_args(argv)
-    if not torch.cuda.is_available():
-        raise SystemExit("this build runs on MI355X only: no CUDA/HIP device visible and there is no CPU fallback")
+    cli.require_gpu()
     device = torch.device("cuda", 0)
     net = DispNetS()
     cli.load_pretrained(net, args.pretrained_disp)
     net.to(device)
     loader = depth_validation_set(args.val_depth_root, args.height, args.width).loader(args.batch_size)
-    metrics = cli.validate_depth(net, loader, device, crop=not args.no_crop, median_scaling=not args.no_median_scaling)
-    print(cli.format_depth_metrics(metrics), flush=True)
+    metrics = validation.validate_depth(net, loader, device, crop=not args.no_crop, median_scaling=not args.no_median_scaling)
+    print(validation.format_depth_metrics(metrics), flush=True)
     return metrics
 
 

@@ -292,6 +292,22 @@ def join_aux_streams():
         cur.wait_stream(s)
 
 
+_WORKSPACES = {}     # (device, stream, key) -> scratch buffer
+
+
+def workspace(key, n, dtype, device):
+    """Scratch of ``n`` elements for one call of a C entry, cached per ``key`` (the entry and the sizes that fix n) and current
+    stream: calls of one stream are ordered, so they can share it.  During a HIP-graph capture it comes from the capture's
+    private pool instead.  (dvf/conv.py::_workspace, which grows and serves side streams, is a different object.)"""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(n, device=device, dtype=dtype)
+    slot = (device, stream_raw(), key)
+    buf = _WORKSPACES.get(slot)
+    if buf is None:
+        _WORKSPACES[slot] = buf = torch.empty(n, device=device, dtype=dtype)
+    return buf
+
+
 PACK_EPOCH = 0  # manual invalidation of every packed weight copy (FlatAdam bumps a per-parameter epoch instead: dvf/conv.py::_stamp)
 
 

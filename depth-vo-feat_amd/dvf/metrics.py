@@ -6,30 +6,11 @@ reference's ``compute_errors`` (loss_functions_sfm.py:80-116) with the rmse colu
 is torch.median's lower median, found exactly.  ``reduce_rows`` averages rows over the images that have a valid pixel."""
 import torch
 
+from depth_eval import garg_rect
 from . import lib as L
 
 COLUMNS = ("abs_diff", "abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3", "n_valid", "med_gt", "med_pred", "n_nan")
 METRICS = COLUMNS[:8]
-
-_WS = {}   # (device, stream, B, H, W) -> workspace
-
-
-def garg_rect(h, w):
-    """(y1, y2, x1, x2) of the Garg crop, the int(...) constants of loss_functions_sfm.py:92-93."""
-    return int(0.40810811 * h), int(0.99189189 * h), int(0.03594771 * w), int(0.96405229 * w)
-
-
-def _workspace(B, H, W, device):
-    """Scratch of one call, cached per shape and stream (calls of one stream are ordered, so they can share it); during a
-    HIP-graph capture it comes from the capture's private pool instead, as dvf/conv.py::_workspace does."""
-    n = int(L.lib().dvf_depth_metrics_ws_floats(B, H, W))
-    if torch.cuda.is_current_stream_capturing():
-        return torch.empty(n, device=device, dtype=torch.float32), n
-    key = (device, L.stream_raw(), B, H, W)
-    buf = _WS.get(key)
-    if buf is None:
-        _WS[key] = buf = torch.empty(n, device=device, dtype=torch.float32)
-    return buf, n
 
 
 def depth_metrics(gt, pred, crop=True, min_depth=0.0, max_depth=80.0, clamp=(1e-3, 80.0), median_scaling=True, reclamp=False,
@@ -45,7 +26,8 @@ def depth_metrics(gt, pred, crop=True, min_depth=0.0, max_depth=80.0, clamp=(1e-
     B, H, W = gt.shape
     y1, y2, x1, x2 = rect if rect is not None else (garg_rect(H, W) if crop else (0, H, 0, W))
     out = torch.empty(B, 12, device=gt.device, dtype=torch.float32)
-    ws, n = _workspace(B, H, W, gt.device)
+    n = int(L.lib().dvf_depth_metrics_ws_floats(B, H, W))
+    ws = L.workspace(("dvf_depth_metrics", B, H, W), n, torch.float32, gt.device)
     flags = (L.DM_MEDIAN_SCALE if median_scaling else 0) | (L.DM_RECLAMP if reclamp else 0)
     L.check(L.lib().dvf_depth_metrics(gt.data_ptr(), pred.data_ptr(), out.data_ptr(), ws.data_ptr(), n, B, H, W, y1, y2, x1, x2,
                                       float(min_depth), float(max_depth), float(clamp[0]), float(clamp[1]), flags, L.stream()),
@@ -53,8 +35,18 @@ def depth_metrics(gt, pred, crop=True, min_depth=0.0, max_depth=80.0, clamp=(1e-
     return out
 
 
+def sum_rows(rows):
+    """(sum of the first eight columns over the images with n_valid > 0 [8], the number of those images []), on the device."""
+    keep = (rows[:, 8] > 0).to(rows.dtype)
+    return (rows[:, :8] * keep[:, None]).sum(0), keep.sum()
+
+
+def mean_rows(total, count):
+    """sum_rows' two results, of one batch or added up over several, as the mean; zeros when no image has a valid pixel."""
+    return total / count.clamp(min=1.0)
+
+
 def reduce_rows(rows):
     """Mean of the first eight columns over the images with n_valid > 0 ([8], on the device, no synchronisation; zeros when
     no image has a valid pixel)."""
-    keep = (rows[:, 8] > 0).to(rows.dtype)
-    return (rows[:, :8] * keep[:, None]).sum(0) / keep.sum().clamp(min=1.0)
+    return mean_rows(*sum_rows(rows))

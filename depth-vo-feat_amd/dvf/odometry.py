@@ -8,15 +8,11 @@ snippet errors of inference.py:72-88; their definition is odometry_eval.py's tra
 trajectory_errors / snippet_errors.  Nothing here synchronises; every result is ordered on the current stream."""
 import torch
 
+# (ALIGN_MODES: index = DVF_ALIGN_* of include/dvf_hip.h)
+from odometry_eval import ALIGN_MODES, FIRST_FRAME, FRAME_STEP, SEGMENT_LENGTHS
 from . import lib as L
 
-SEGMENT_LENGTHS = (100, 200, 300, 400, 500, 600, 700, 800)
-FIRST_FRAME, FRAME_STEP = 9, 10
-
-ALIGN_MODES = ("none", "scale", "scale_7dof", "6dof", "7dof")      # index = DVF_ALIGN_* of include/dvf_hip.h
 SNIPPET_LENGTHS = (2, 8)                                           # inclusive
-
-_WS = {}   # (device, stream, n, size query) -> workspace
 
 
 def _dev64(t, name):
@@ -27,19 +23,6 @@ def _dev64(t, name):
     if not t.is_contiguous():
         raise RuntimeError(f"{name}: expected a contiguous tensor")
     return t.data_ptr()
-
-
-def _workspace(n, device, query="dvf_odometry_errors_ws_doubles"):
-    """Scratch of one call of the entry whose size ``query`` answers, cached per entry, length and stream; from the capture's
-    private pool during a HIP-graph capture (as dvf/metrics.py::_workspace)."""
-    m = int(getattr(L.lib(), query)(n))
-    if torch.cuda.is_current_stream_capturing():
-        return torch.empty(m, device=device, dtype=torch.float64), m
-    key = (device, L.stream_raw(), n, query)
-    buf = _WS.get(key)
-    if buf is None:
-        _WS[key] = buf = torch.empty(m, device=device, dtype=torch.float64)
-    return buf, m
 
 
 def n_starts(n):
@@ -65,32 +48,6 @@ def chain_poses(rel, offsets=None):
     return world
 
 
-def sequence_errors(gt, res, summary=None):
-    """KITTI segment errors of the trajectory ``res`` against ``gt``, both [n,3,4] fp64 on the device.  Returns (rows,
-    summary): rows [n_starts(n)*8, 6] = [first, r_err/len, t_err/len, len, speed, valid] (start-major, lengths ascending,
-    all zero where the segment does not end inside the sequence) and summary [4] = [sum t_err/len, sum r_err/len, valid
-    rows, path length of gt].  A ``summary`` passed in has the first three added to it in place (several sequences, one
-    pass)."""
-    _dev64(gt, "gt")
-    _dev64(res, "res")
-    if gt.dim() != 3 or tuple(gt.shape[1:]) != (3, 4) or gt.shape != res.shape or gt.shape[0] < 1:
-        raise ValueError(f"sequence_errors: gt and res must be [n,3,4] of one size, n >= 1, got {tuple(gt.shape)} and "
-                         f"{tuple(res.shape)}")
-    n = gt.shape[0]
-    accumulate = summary is not None
-    if accumulate:
-        _dev64(summary, "summary")
-        if summary.numel() != 4:
-            raise ValueError("sequence_errors: summary must hold 4 doubles")
-    else:
-        summary = torch.empty(4, device=gt.device, dtype=torch.float64)
-    rows = torch.empty(n_starts(n) * len(SEGMENT_LENGTHS), 6, device=gt.device, dtype=torch.float64)
-    ws, m = _workspace(n, gt.device)
-    L.check(L.lib().dvf_odometry_errors(gt.data_ptr(), res.data_ptr(), n, rows.data_ptr() if rows.numel() else None,
-                                        summary.data_ptr(), int(accumulate), ws.data_ptr(), m, L.stream()), "dvf_odometry_errors")
-    return rows, summary
-
-
 def _pair(gt, res, what, n_min=1):
     """The checks every (gt, res) entry shares, before any launch; returns n."""
     _dev64(gt, "gt")
@@ -99,6 +56,28 @@ def _pair(gt, res, what, n_min=1):
         raise ValueError(f"{what}: gt and res must be [n,3,4] of one size, n >= {n_min}, got {tuple(gt.shape)} and "
                          f"{tuple(res.shape)}")
     return gt.shape[0]
+
+
+def sequence_errors(gt, res, summary=None):
+    """KITTI segment errors of the trajectory ``res`` against ``gt``, both [n,3,4] fp64 on the device.  Returns (rows,
+    summary): rows [n_starts(n)*8, 6] = [first, r_err/len, t_err/len, len, speed, valid] (start-major, lengths ascending,
+    all zero where the segment does not end inside the sequence) and summary [4] = [sum t_err/len, sum r_err/len, valid
+    rows, path length of gt].  A ``summary`` passed in has the first three added to it in place (several sequences, one
+    pass)."""
+    n = _pair(gt, res, "sequence_errors")
+    accumulate = summary is not None
+    if accumulate:
+        _dev64(summary, "summary")
+        if summary.numel() != 4:
+            raise ValueError("sequence_errors: summary must hold 4 doubles")
+    else:
+        summary = torch.empty(4, device=gt.device, dtype=torch.float64)
+    rows = torch.empty(n_starts(n) * len(SEGMENT_LENGTHS), 6, device=gt.device, dtype=torch.float64)
+    m = int(L.lib().dvf_odometry_errors_ws_doubles(n))
+    ws = L.workspace(("dvf_odometry_errors", n), m, torch.float64, gt.device)
+    L.check(L.lib().dvf_odometry_errors(gt.data_ptr(), res.data_ptr(), n, rows.data_ptr() if rows.numel() else None,
+                                        summary.data_ptr(), int(accumulate), ws.data_ptr(), m, L.stream()), "dvf_odometry_errors")
+    return rows, summary
 
 
 def align(gt, res, mode):
@@ -113,7 +92,8 @@ def align(gt, res, mode):
     n = _pair(gt, res, f"align ({mode})", 3 if m >= 2 else 1)
     transform = torch.empty(16, device=gt.device, dtype=torch.float64)
     aligned = torch.empty_like(res)
-    ws, size = _workspace(n, gt.device, "dvf_trajectory_align_ws_doubles")
+    size = int(L.lib().dvf_trajectory_align_ws_doubles(n))
+    ws = L.workspace(("dvf_trajectory_align", n), size, torch.float64, gt.device)
     L.check(L.lib().dvf_trajectory_align(gt.data_ptr(), res.data_ptr(), n, m, transform.data_ptr(), ws.data_ptr(), size, L.stream()),
             "dvf_trajectory_align")
     L.check(L.lib().dvf_trajectory_apply(res.data_ptr(), transform.data_ptr(), n, int(m == 0), aligned.data_ptr(), L.stream()),
@@ -126,7 +106,8 @@ def trajectory_errors(gt, res):
     [n,3,4] fp64 on the device; NaN for the two RPE values when n = 1.  Definition: odometry_eval.trajectory_errors."""
     n = _pair(gt, res, "trajectory_errors")
     out = torch.empty(4, device=gt.device, dtype=torch.float64)
-    ws, size = _workspace(n, gt.device, "dvf_trajectory_errors_ws_doubles")
+    size = int(L.lib().dvf_trajectory_errors_ws_doubles(n))
+    ws = L.workspace(("dvf_trajectory_errors", n), size, torch.float64, gt.device)
     L.check(L.lib().dvf_trajectory_errors(gt.data_ptr(), res.data_ptr(), n, out.data_ptr(), ws.data_ptr(), size, L.stream()),
             "dvf_trajectory_errors")
     return out
@@ -148,7 +129,8 @@ def snippet_errors(gt, res, length=5, summary=None):
     else:
         summary = torch.empty(5, device=gt.device, dtype=torch.float64)
     rows = torch.empty(max(n - length + 1, 0), 2, device=gt.device, dtype=torch.float64)
-    ws, size = _workspace(n, gt.device, "dvf_snippet_errors_ws_doubles")
+    size = int(L.lib().dvf_snippet_errors_ws_doubles(n))
+    ws = L.workspace(("dvf_snippet_errors", n), size, torch.float64, gt.device)
     L.check(L.lib().dvf_snippet_errors(gt.data_ptr(), res.data_ptr(), n, int(length), rows.data_ptr() if rows.numel() else None,
                                        summary.data_ptr(), int(accumulate), ws.data_ptr(), size, L.stream()), "dvf_snippet_errors")
     return rows, summary

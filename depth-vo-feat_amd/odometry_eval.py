@@ -11,7 +11,7 @@ The reference tool cannot be imported here (caffe, h5py, cv2), so these follow i
 checked by known-answer tests (tests/test_odometry_eval.py): parity unpinned against the reference itself.
 
 Run as a script (``python odometry_eval.py --pretrained-pose CKPT --val-root DIR --sequences 09 10``) it evaluates a pose
-checkpoint on the GPU through dvf.cli.validate_odometry / dvf.odometry (csrc/odometry.hip), for which se3_cam2world,
+checkpoint on the GPU through dvf.validation.validate_odometry / dvf.odometry (csrc/odometry.hip), for which se3_cam2world,
 sequence_errors and overall_error below, and with ``--align MODE`` the four alignment functions, are the definition; importing
 this module needs numpy only."""
 import os
@@ -22,11 +22,15 @@ SEGMENT_LENGTHS = (100, 200, 300, 400, 500, 600, 700, 800)     # metres (evaluat
 FIRST_FRAME, FRAME_STEP, FRAME_PERIOD = 9, 10, 0.1             # :456,:458 and the 10 Hz speed constant of :482
 
 
+def pose_line(se3):
+    """One pose ([3,4] or [4,4]) as a KITTI line: the 3x4 [R|t] in row-major order, 12 numbers (inference.py:43-61)."""
+    return " ".join(str(v) for v in np.asarray(se3, dtype=np.float64)[:3, :4].reshape(12)) + "\n"
+
+
 def save_result_poses(se3, output_dir, filename):
-    """Append one pose as a KITTI line: the 3x4 [R|t] in row-major order, 12 numbers (inference.py:43-61)."""
-    se3 = np.asarray(se3, dtype=np.float64)
+    """Append one pose as a KITTI line (pose_line)."""
     with open(os.path.join(output_dir, filename), "a") as f:
-        f.write(" ".join(str(v) for v in se3[:3, :4].reshape(12)) + "\n")
+        f.write(pose_line(se3))
 
 
 def se3_cam2world(rel_poses):
@@ -210,15 +214,15 @@ def overall_error(seq_err):
 
 
 def main(argv=None):
-    """Evaluate a pose checkpoint on KITTI odometry sequences on the GPU (dvf.cli.validate_odometry: the functions above are
-    its definition, restated in csrc/odometry.hip) and print one ``Odometry:`` line per sequence, then the line over all
+    """Evaluate a pose checkpoint on KITTI odometry sequences on the GPU (dvf.validation.validate_odometry: the functions above
+    are its definition, restated in csrc/odometry.hip) and print one ``Odometry:`` line per sequence, then the line over all
     segments of all sequences (the line train.py --val-odometry prints after every epoch).  torch and the GPU are touched
     only here: importing this module stays numpy-only."""
     import argparse
     import torch
     from PoseExpNet_sfm import PoseExpNet
     from dataset import odometry_sequences
-    from dvf import cli
+    from dvf import cli, validation
     parser = argparse.ArgumentParser(description="KITTI odometry evaluation of a pose network on MI355X",
                                      formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     parser.add_argument("--pretrained-pose", required=True, metavar="PATH",
@@ -228,7 +232,7 @@ def main(argv=None):
     parser.add_argument("--height", type=int, default=256)
     parser.add_argument("--width", type=int, default=832)
     parser.add_argument("-b", "--batch-size", type=int, default=4)
-    parser.add_argument("--pose-convention", choices=list(cli.POSE_CONVENTIONS), default="se3",
+    parser.add_argument("--pose-convention", choices=list(validation.POSE_CONVENTIONS), default="se3",
                         help="se3 = (w, u) through the exponential map, what validate() scores; euler = (t, r-euler), what "
                              "train.py's photometric loss trains the outputs as")
     parser.add_argument("--output-dir", default=None, metavar="DIR", help="write <seq>.txt, one KITTI pose line per frame")
@@ -238,8 +242,7 @@ def main(argv=None):
                              "scale of 7dof alone): the Odometry line is then that of the aligned trajectory, a Trajectory line "
                              "with ATE, RPE and the 5-frame-snippet ATE follows it, and --output-dir also gets <seq>_aligned.txt")
     args = parser.parse_args(argv)
-    if not torch.cuda.is_available():
-        raise SystemExit("this build runs on MI355X only: no CUDA/HIP device visible and there is no CPU fallback")
+    cli.require_gpu()
     device = torch.device("cuda", 0)
     net = PoseExpNet(nb_ref_imgs=2, output_exp=True)                     # validate()'s call feeds two reference views
     cli.load_pretrained(net, args.pretrained_pose, strict=False)
@@ -247,15 +250,15 @@ def main(argv=None):
     sequences = odometry_sequences(args.val_root, args.sequences, args.height, args.width)
     if not sequences:
         raise SystemExit(f"no sequence of {args.sequences} under {args.val_root}/sequences")
-    metrics = cli.validate_odometry(net, sequences, device, args.batch_size, convention=args.pose_convention,
-                                    output_dir=args.output_dir, align=args.align)
+    metrics = validation.validate_odometry(net, sequences, device, args.batch_size, convention=args.pose_convention,
+                                           output_dir=args.output_dir, align=args.align)
     for name, m in metrics["per_sequence"].items():
-        print(cli.format_odometry(m, name), flush=True)
+        print(validation.format_odometry(m, name), flush=True)
         if args.align is not None:
-            print(cli.format_trajectory(m, name), flush=True)
-    print(cli.format_odometry(metrics), flush=True)
+            print(validation.format_trajectory(m, name), flush=True)
+    print(validation.format_odometry(metrics), flush=True)
     if args.align is not None:
-        print(cli.format_trajectory(metrics), flush=True)
+        print(validation.format_trajectory(metrics), flush=True)
     return metrics
 
 

@@ -27,7 +27,7 @@ import torch  # noqa: E402
 
 from DispNetS import DispNetS  # noqa: E402
 from PoseExpNet_sfm import PoseExpNet  # noqa: E402
-from dvf import cli  # noqa: E402
+from dvf import cli, validation  # noqa: E402
 from dvf.odometry import ALIGN_MODES  # noqa: E402
 from dvf.steps import train_sfm_losses  # noqa: E402
 
@@ -60,12 +60,12 @@ parser.add_argument("--val-root", default=None, help="KITTI odometry tree for va
 parser.add_argument("--val-depth-root", default=None, metavar="DIR",
                     help="depth validation tree (val.txt, image/<stem>.png|jpg, depth/<stem>.npy in metres, 0 = no measurement): "
                          "after every epoch rank 0 prints the Eigen depth metrics of the depth network against it "
-                         "(dvf.cli.validate_depth) and best_depth_checkpoint.pth.tar is saved on the best abs_rel")
+                         "(dvf.validation.validate_depth) and best_depth_checkpoint.pth.tar is saved on the best abs_rel")
 parser.add_argument("--val-odometry", action="store_true",
                     help="needs --val-root: after every epoch rank 0 also chains the pose network's output over each of "
                          "--test-sequences into a trajectory and prints its KITTI odometry errors (t_err in %%, r_err in deg / 100 m, "
-                         "computed on the GPU: dvf.cli.validate_odometry); best_odometry_checkpoint.pth.tar is saved on the best t_err")
-parser.add_argument("--pose-convention", choices=list(cli.POSE_CONVENTIONS), default="se3",
+                         "computed on the GPU: dvf.validation.validate_odometry); best_odometry_checkpoint.pth.tar is saved on the best t_err")
+parser.add_argument("--pose-convention", choices=list(validation.POSE_CONVENTIONS), default="se3",
                     help="how --val-odometry reads the pose network's six outputs: se3 = (w, u) through the exponential map, what "
                          "validate() scores; euler = (t, r-euler), what the photometric loss of this script trains them as")
 parser.add_argument("--val-odometry-align", choices=list(ALIGN_MODES), default=None, metavar="MODE",
@@ -107,30 +107,32 @@ def main():
 
     terms = ["total", "photo", "smooth", "lr"] + (["exp"] if args.mask_loss_weight > 0 else []) + \
         (["automask"] if args.auto_mask else [])
-    val_fn = None
+    validators = []
     if args.val_root and args._rank == 0:
         from dataset import pose_framework_KITTI
         val_set = pose_framework_KITTI(args.val_root, args.test_sequences, img_height=args.height, img_width=args.width,
                                        shuffle=False)
         val_loader = torch.utils.data.DataLoader(val_set, batch_size=args.batch_size, shuffle=False, num_workers=0)
-        val_fn = lambda: cli.validate(pose_exp_net, val_loader, args._device)      # noqa: E731
-    depth_kwargs = {}
+        # (ckpts=None: the reference's criterion for best_vo / best_depth, in place of the training loss)
+        validators.append(cli.Validator(lambda _: validation.validate(pose_exp_net, val_loader, args._device), float,
+                                        validation.pose_epoch_lines, None))
     if args.val_depth_root and args._rank == 0:
         from dataset import depth_validation_set
         depth_loader = depth_validation_set(args.val_depth_root, args.height, args.width).loader(args.batch_size)
-        depth_kwargs = {"depth_val_fn": lambda: cli.validate_depth(disp_net, depth_loader, args._device),
-                        "depth_ckpt": ("best_depth_checkpoint.pth.tar", disp_net)}
-    odometry_kwargs = {}
+        validators.append(cli.Validator(lambda _: validation.validate_depth(disp_net, depth_loader, args._device),
+                                        lambda m: m["abs_rel"], validation.depth_epoch_lines,
+                                        [("best_depth_checkpoint.pth.tar", disp_net)]))
     if args.val_odometry and args._rank == 0:
         from dataset import odometry_sequences
         sequences = odometry_sequences(args.val_root, args.test_sequences, args.height, args.width)
-        odometry_kwargs = {"odometry_val_fn": lambda: cli.validate_odometry(pose_exp_net, sequences, args._device, args.batch_size,
-                                                                           convention=args.pose_convention,
-                                                                           align=args.val_odometry_align),
-                           "odometry_ckpt": ("best_odometry_checkpoint.pth.tar", pose_exp_net)}
+        validators.append(cli.Validator(lambda _: validation.validate_odometry(pose_exp_net, sequences, args._device, args.batch_size,
+                                                                               convention=args.pose_convention,
+                                                                               align=args.val_odometry_align),
+                                        lambda m: m["t_err"], validation.odometry_epoch_lines,
+                                        [("best_odometry_checkpoint.pth.tar", pose_exp_net)]))
     cli.run_training(args, [disp_net, pose_exp_net], loss_fn, args.lr, (args.momentum, args.beta), args.weight_decay,
                      terms, [("best_vo_checkpoint.pth.tar", pose_exp_net), ("best_depth_checkpoint.pth.tar", disp_net)],
-                     n_views=max(2, args.nb_ref_imgs), val_fn=val_fn, **depth_kwargs, **odometry_kwargs)
+                     n_views=max(2, args.nb_ref_imgs), validators=validators)
 
 
 if __name__ == "__main__":

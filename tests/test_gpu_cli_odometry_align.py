@@ -1,4 +1,4 @@
-"""dvf.cli.validate_odometry(align=...), odometry_eval.py --align and train.py --val-odometry-align end to end on the small
+"""dvf.validation.validate_odometry(align=...), odometry_eval.py --align and train.py --val-odometry-align end to end on the small
 KITTI-odometry-shaped tree of tests/test_gpu_odometry.py (64x208, 20 frames), its ground truth a chained walk of 12 m steps with
 a slow turn (align_ref.end_to_end_gt: positions that are not collinear; the straight line of odometry_ref.end_to_end_gt has no
 unique alignment rotation, its sv[1] and sv[2] are exactly 0).
@@ -48,9 +48,9 @@ def _close(name, got, want):
 
 
 def test_validate_odometry_aligned_fields_are_the_definition_of_the_returned_chain(tree, net, tmp_path):
-    from dvf import cli
+    from dvf import validation
     gt, _, seqs = tree
-    out = cli.validate_odometry(net, seqs, torch.device(DEV, 0), 4, align="7dof", keep=True, output_dir=str(tmp_path))
+    out = validation.validate_odometry(net, seqs, torch.device(DEV, 0), 4, align="7dof", keep=True, output_dir=str(tmp_path))
     world = out["world"].cpu().numpy()
     c, rot, t, sv = oe.trajectory_alignment(gt, world, "7dof")
     assert (sv[1] + sv[2]) / sv[0] >= A.CONDITION                        # the chain of a random network is not collinear
@@ -78,34 +78,35 @@ def test_validate_odometry_aligned_fields_are_the_definition_of_the_returned_cha
     _close("t_err", out["t_err"], 100.0 * t_err)
     # (r_err through arccos at ~1e-2 rad: the bound of tests/test_gpu_odometry.py)
     _close("r_err", out["r_err"], r_err * deg * 100.0)
-    line = cli.format_trajectory(out)
+    line = validation.format_trajectory(out)
     assert line.startswith("Trajectory: align 7dof scale ") and line.endswith(f"snippets {N - 4}")
-    assert cli.format_trajectory(per, "00").endswith(f"snippets {N - 4} seq 00")
+    assert validation.format_trajectory(per, "00").endswith(f"snippets {N - 4} seq 00")
     for name, key in (("00.txt", "world"), ("00_aligned.txt", "aligned")):
         back = oe.load_poses(os.path.join(tmp_path, name))
         assert np.array_equal(np.stack([back[i] for i in range(N)])[:, :3], out[key].cpu().numpy())
-    raw = cli.validate_odometry(net, seqs, torch.device(DEV, 0), 4)
+    raw = validation.validate_odometry(net, seqs, torch.device(DEV, 0), 4)
     assert raw["t_err"] != out["t_err"]                                  # the alignment changed the score
 
 
 def test_validate_odometry_synchronises_once_before_the_file_writing():
-    from dvf import cli
-    body = inspect.getsource(cli.validate_odometry)
-    head = body[:body.index("if output_dir is not None")]
+    from dvf import validation
+    body = inspect.getsource(validation.validate_odometry)
+    head = (inspect.getsource(validation.relative_poses) + inspect.getsource(validation.score_trajectories) +
+            body[:body.index("write_trajectories(")])
     assert head.count(".tolist()") == 1 and ".cpu()" not in head and ".item()" not in head and "synchronize" not in head
 
 
 def test_without_align_the_dict_has_todays_keys_and_none_aligns_nothing(tree, net):
-    from dvf import cli
+    from dvf import validation
     gt, _, seqs = tree
-    out = cli.validate_odometry(net, seqs, torch.device(DEV, 0), 4, keep=True)
+    out = validation.validate_odometry(net, seqs, torch.device(DEV, 0), 4, keep=True)
     assert sorted(out) == ["offsets", "per_sequence", "r_err", "rel", "segments", "t_err", "world"]
     assert sorted(out["per_sequence"]["00"]) == ["path_length", "r_err", "segments", "t_err"]
-    same = cli.validate_odometry(net, seqs, torch.device(DEV, 0), 4, align="none", keep=True)
+    same = validation.validate_odometry(net, seqs, torch.device(DEV, 0), 4, align="none", keep=True)
     assert same["t_err"] == out["t_err"] and same["r_err"] == out["r_err"] and same["per_sequence"]["00"]["scale"] == 1.0
     assert torch.equal(same["aligned"], same["world"]) and torch.equal(same["world"], out["world"])
     with pytest.raises(ValueError):
-        cli.validate_odometry(net, seqs, torch.device(DEV, 0), 4, align="sim3")
+        validation.validate_odometry(net, seqs, torch.device(DEV, 0), 4, align="sim3")
 
 
 def test_odometry_eval_prints_trajectory_lines_only_with_align(tree, net, tmp_path, capsys):

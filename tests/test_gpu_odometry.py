@@ -1,4 +1,4 @@
-"""dvf_pose_chain / dvf_odometry_errors / dvf.cli.validate_odometry on the GPU against the numpy definition
+"""dvf_pose_chain / dvf_odometry_errors / dvf.validation.validate_odometry on the GPU against the numpy definition
 (odometry_eval.py: se3_cam2world, sequence_errors, overall_error; inputs from tests/odometry_ref.py).
 
 Bound: conftest.rel_err < 1e-9 for world poses and for the t_err/len, r_err/len and speed columns; first, length, the valid
@@ -174,14 +174,14 @@ def tree(tmp_path_factory):
 @pytest.mark.parametrize("convention", ["se3", "euler"])
 def test_validate_odometry_end_to_end(tree, tmp_path, convention):
     from PoseExpNet_sfm import PoseExpNet
-    from dvf import cli
+    from dvf import validation
     gt, seqs = tree
     assert np.array_equal(seqs[0][2], gt[:, :3])
     torch.manual_seed(0)
     net = PoseExpNet(nb_ref_imgs=2, output_exp=True)
     net.init_weights()
     net.to(DEV).train()
-    out = cli.validate_odometry(net, seqs, torch.device(DEV, 0), 4, convention=convention, output_dir=str(tmp_path), keep=True)
+    out = validation.validate_odometry(net, seqs, torch.device(DEV, 0), 4, convention=convention, output_dir=str(tmp_path), keep=True)
     assert net.training                                                  # the mode is restored
     rel = out["rel"].cpu().numpy()
     assert rel.dtype == np.float32 and rel.shape == (19, 4, 4) and np.all(rel[:, 3] == np.array([0, 0, 0, 1], dtype=np.float32))
@@ -202,5 +202,5 @@ def test_validate_odometry_end_to_end(tree, tmp_path, convention):
     back = oe.load_poses(os.path.join(tmp_path, "00.txt"))
     assert sorted(back) == list(range(20))
     assert np.array_equal(np.stack([back[i] for i in range(20)])[:, :3], out["world"].cpu().numpy())
-    other = cli.validate_odometry(net, seqs, torch.device(DEV, 0), 4, convention="euler" if convention == "se3" else "se3", keep=True)
+    other = validation.validate_odometry(net, seqs, torch.device(DEV, 0), 4, convention="euler" if convention == "se3" else "se3", keep=True)
     assert not torch.equal(other["rel"], out["rel"])                     # the two readings of the six outputs differ
