@@ -142,10 +142,14 @@ constexpr int PIPE_MAXNPI = 32;    // patch pieces per channel (per-channel patc
 // blocked CPU GEMM's instead of one sequential fmaf chain (a 1161-term chain is 2.6x further from fp64 than torch's CPU
 // kernels, tools/r3/layer_noise.py).  The second set costs no occupancy (the kernel's register count is set by the
 // producer waves' offset tables, 141-155 VGPRs in every variant) but 1-2 % of a step when every instantiation carries it.
-template <int MT, int NT, int WM, int CKH, int TBU, int BLK = 0>
-__global__ __launch_bounds__(PIPE_THREADS_4P) void conv_pipe_kernel(const PipeArgs a) {
+// NPMAX = patch pieces per channel the producers' tables hold.  PIPE_MAXNPI: every plan.  Less (PIPE_LR_NPI, below): the
+// low-register form, compiled for four waves per SIMD so that two 8-wave blocks share a CU.
+template <int MT, int NT, int WM, int CKH, int TBU, int BLK = 0, int NPMAX = PIPE_MAXNPI>
+__global__ __launch_bounds__(PIPE_THREADS_4P) __attribute__((amdgpu_waves_per_eu(NPMAX < PIPE_MAXNPI ? 4 : 0)))
+void conv_pipe_kernel(const PipeArgs a) {
     constexpr int CK = 2 * CKH, VW = CKH >= 4 ? 4 : CKH, CPG = CKH / VW, MTW = MT * WM;
     constexpr int UNITF = TBU * MTW * 64 * VW;             // packed floats per unit
+    static_assert(NPMAX >= 6 && NPMAX <= PIPE_MAXNPI, "by_np dispatches exact piece counts up to 6");
     typedef typename fvec<VW>::type avec;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int stage_floats = a.SLmax + CK * a.PSRmax;
@@ -222,15 +226,15 @@ __global__ __launch_bounds__(PIPE_THREADS_4P) void conv_pipe_kernel(const PipeAr
 
         // per-lane source offset of every patch piece: offset inside one image plane + (image in the batch group) x (image
         // stride of the segment the producer is in); bit 31 set (OOB) = outside the image / the batch -> reads 0.0f
-        unsigned pvf[PIPE_MAXNPI];
-        unsigned pbn4[PIPE_MAXNPI / 4];                    // image inside the block's batch group (8-bit fields)
+        unsigned pvf[NPMAX];
+        unsigned pbn4[(NPMAX + 3) / 4];                    // image inside the block's batch group (8-bit fields)
 #pragma unroll
-        for (int q = 0; q < PIPE_MAXNPI / 4; ++q) pbn4[q] = 0u;
+        for (int q = 0; q < (NPMAX + 3) / 4; ++q) pbn4[q] = 0u;
         {
             const int per_img = geo.PH * RS;
             const float inv_img = 1.0f / (float)per_img, inv_rs = 1.0f / (float)RS;
 #pragma unroll
-            for (int kk = 0; kk < PIPE_MAXNPI; ++kk) {
+            for (int kk = 0; kk < NPMAX; ++kk) {
                 pvf[kk] = OOB;
                 if (kk < NPIu) {
                     // first float of this lane in piece kk: a piece is 64 lanes x 1 float, or 64 lanes x 4 floats (x4)
@@ -278,7 +282,7 @@ __global__ __launch_bounds__(PIPE_THREADS_4P) void conv_pipe_kernel(const PipeAr
             if (a.BN > 1) {                                // (valid offsets stay below 2^31: bit 31 keeps marking OOB lanes)
                 const unsigned delta = img - img_cur;
 #pragma unroll
-                for (int kk = 0; kk < PIPE_MAXNPI; ++kk)
+                for (int kk = 0; kk < NPMAX; ++kk)
                     if (kk < NPIu) pvf[kk] = (pvf[kk] >> 31) ? OOB : pvf[kk] + ((pbn4[kk >> 2] >> ((kk & 3) * 8)) & 255u) * delta;
             }
             img_cur = img;
@@ -355,8 +359,12 @@ __global__ __launch_bounds__(PIPE_THREADS_4P) void conv_pipe_kernel(const PipeAr
                 case 5: chunk_loop(lanec, integral_constant<int, 5>{}, std::true_type{}); break;
                 case 6: chunk_loop(lanec, integral_constant<int, 6>{}, std::true_type{}); break;
                 default:
-                    if (NPIu <= 12) chunk_loop(lanec, integral_constant<int, 12>{}, std::false_type{});
-                    else chunk_loop(lanec, integral_constant<int, PIPE_MAXNPI>{}, std::false_type{});
+                    if constexpr (NPMAX > 12) {
+                        if (NPIu <= 12) chunk_loop(lanec, integral_constant<int, 12>{}, std::false_type{});
+                        else chunk_loop(lanec, integral_constant<int, NPMAX>{}, std::false_type{});
+                    } else {
+                        chunk_loop(lanec, integral_constant<int, NPMAX>{}, std::false_type{});
+                    }
             }
         };
         if (a.x4) by_np(integral_constant<int, 16>{});
@@ -378,19 +386,26 @@ __global__ __launch_bounds__(PIPE_THREADS_4P) void conv_pipe_kernel(const PipeAr
     }
     const int NU = c.NTG * CPG;                            // units per chunk
     int opy[NT], opx[NT], opn[NT];
-    int bj[NT][VW];                                        // B-fragment base (floats) per tile and channel pair
+    // LR, the low-register form: what follows keeps fewer values alive across the chunk loop -- one B-fragment base per tile (the
+    // channel pair's offset goes into the scalar row address), the tile positions formed again for the epilogue, one chunk
+    // loop per form of the consumer.  Same loads, same MFMAs in the same order: the results are bit-identical.
+    constexpr bool LR = NPMAX < PIPE_MAXNPI;
+    int bj[NT][LR ? 1 : VW];                               // B-fragment base (floats) per tile and channel pair
     const int pxl = nl & (SW - 1), pyl = (nl >> a.lsw) & (SH - 1), pnl = nl >> (a.lsw + a.lsh);
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
+    auto tile_pos = [&](int i, int pxv, int pyv, int pnv) __attribute__((always_inline)) {
         const int q = wn * NT + i, tx = q % a.TGX, tyn = q / a.TGX, ty = tyn % a.TGY, tn = tyn / a.TGY;
         const int SN = 32 >> (a.lsw + a.lsh);
-        opy[i] = ty * SH + pyl;
-        opx[i] = tx * SW + pxl;
-        opn[i] = tn * SN + pnl;
+        opy[i] = ty * SH + pyv;
+        opx[i] = tx * SW + pxv;
+        opn[i] = tn * SN + pnv;
+    };
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        tile_pos(i, pxl, pyl, pnl);
         // x4: rows in image order behind XA floats of margin (stride-2 tiles read every other float)
         const int bbase = kh * PSR + (opn[i] * geo.PH + opy[i] * a.IS) * RS + (a.x4 ? geo.XA + opx[i] * a.IS : opx[i]);
 #pragma unroll
-        for (int j = 0; j < VW; ++j) bj[i][j] = bbase + j * 2 * PSR;
+        for (int j = 0; j < (LR ? 1 : VW); ++j) bj[i][j] = bbase + j * 2 * PSR;
     }
     f32x16 acc[MT][NT];
     f32x16 asum[BLK ? MT : 1][BLK ? NT : 1];              // (BLK) running sum of the banked partial sums
@@ -423,10 +438,10 @@ __global__ __launch_bounds__(PIPE_THREADS_4P) void conv_pipe_kernel(const PipeAr
         // B rows of the next unit for channel pair j (all tiles): TBU consecutive floats of one patch row each
         auto load_bj = [&](auto bufc, auto jc) {
             constexpr int buf = decltype(bufc)::value, j = decltype(jc)::value;
-            const float *prow0 = patch + (lta * RS + lcpg * (2 * VW) * PSR);
+            const float *prow0 = patch + (lta * RS + (lcpg * (2 * VW) + (LR ? 2 * j : 0)) * PSR);
 #pragma unroll
             for (int i = 0; i < NT; ++i) {
-                const float *prow = prow0 + bj[i][j];
+                const float *prow = prow0 + bj[i][LR ? 0 : j];
                 if constexpr (IS == 1) {
 #pragma unroll
                     for (int u = 0; u < TBE; ++u) bf[buf][u][i][j] = prow[u];
@@ -524,33 +539,55 @@ __global__ __launch_bounds__(PIPE_THREADS_4P) void conv_pipe_kernel(const PipeAr
     unsigned long long t_loop0 = 0, t_loop1 = 0, tb0 = 0, tb1 = 0, w_bar = 0;
     DVF_STAMP(a, t_loop0);
     if (!DVF_DBG(a, 8)) {
-        int st = 0, since = 0;
-        for (int g = g_begin; g < g_end; ++g) {
-            DVF_STAMP(a, tb0);
-            __syncthreads();          // chunk g has landed (its producer waited for it) and chunk g-1 is fully consumed
-            DVF_STAMP(a, tb1);
-            w_bar += tb1 - tb0;
-            if (!DVF_DBG(a, 4)) {
-                using TBfull = std::integral_constant<int, TBU>;
-                using TBless = std::integral_constant<int, (TBU > 1 ? TBU - 1 : 1)>;
-                if (a.IS == 2 && !a.x4) consume(st, std::integral_constant<int, 2>{}, TBfull{});      // (de-interleaved rows)
-                else if (TBU > 1 && c.TB == TBU - 1 && !DVF_DBG(a, 64)) consume(st, std::integral_constant<int, 1>{}, TBless{});
-                else consume(st, std::integral_constant<int, 1>{}, TBfull{});
-            }
-            if constexpr (BLK) {
-                if (++since == a.blk) {     // (uniform)
-                    since = 0;
-#pragma unroll
-                    for (int m = 0; m < MT; ++m)
-#pragma unroll
-                        for (int i = 0; i < NT; ++i) {
-                            asum[m][i] += acc[m][i];
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) acc[m][i][r] = 0.f;
-                        }
+        using IS1 = std::integral_constant<int, 1>;
+        using IS2 = std::integral_constant<int, 2>;
+        using TBfull = std::integral_constant<int, TBU>;
+        using TBless = std::integral_constant<int, (TBU > 1 ? TBU - 1 : 1)>;
+        if constexpr (LR) {
+            // One chunk loop per form of the consumer, chosen once per block: with the choice inside the loop (below) hipcc
+            // keeps the accumulators twice -- a loop-carried set and the consumer's own, copied at every chunk: 32 VGPRs.
+            static_assert(!BLK, "the low-register form has no second accumulator set");
+            auto chunks = [&](auto isc, auto tbec) __attribute__((always_inline)) {
+                int st = 0;
+                for (int g = g_begin; g < g_end; ++g) {
+                    DVF_STAMP(a, tb0);
+                    __syncthreads();
+                    DVF_STAMP(a, tb1);
+                    w_bar += tb1 - tb0;
+                    if (!DVF_DBG(a, 4)) consume(st, isc, tbec);
+                    st = (st + 1 == a.NST) ? 0 : st + 1;
                 }
+            };
+            if (a.IS == 2 && !a.x4) chunks(IS2{}, TBfull{});
+            else if (TBU > 1 && c.TB == TBU - 1 && !DVF_DBG(a, 64)) chunks(IS1{}, TBless{});
+            else chunks(IS1{}, TBfull{});
+        } else {
+            int st = 0, since = 0;
+            for (int g = g_begin; g < g_end; ++g) {
+                DVF_STAMP(a, tb0);
+                __syncthreads();          // chunk g has landed (its producer waited for it) and chunk g-1 is fully consumed
+                DVF_STAMP(a, tb1);
+                w_bar += tb1 - tb0;
+                if (!DVF_DBG(a, 4)) {
+                    if (a.IS == 2 && !a.x4) consume(st, IS2{}, TBfull{});      // (de-interleaved rows)
+                    else if (TBU > 1 && c.TB == TBU - 1 && !DVF_DBG(a, 64)) consume(st, IS1{}, TBless{});
+                    else consume(st, IS1{}, TBfull{});
+                }
+                if constexpr (BLK) {
+                    if (++since == a.blk) {     // (uniform)
+                        since = 0;
+#pragma unroll
+                        for (int m = 0; m < MT; ++m)
+#pragma unroll
+                            for (int i = 0; i < NT; ++i) {
+                                asum[m][i] += acc[m][i];
+#pragma unroll
+                                for (int r = 0; r < 16; ++r) acc[m][i][r] = 0.f;
+                            }
+                    }
+                }
+                st = (st + 1 == a.NST) ? 0 : st + 1;
             }
-            st = (st + 1 == a.NST) ? 0 : st + 1;
         }
     }
     if constexpr (BLK) {
@@ -560,6 +597,12 @@ __global__ __launch_bounds__(PIPE_THREADS_4P) void conv_pipe_kernel(const PipeAr
             for (int i = 0; i < NT; ++i) acc[m][i] += asum[m][i];
     }
 
+    if constexpr (LR) {     // the tile positions again (behind an opaque copy of the lane: not kept in registers through the loop)
+        int nlv = nl;
+        asm volatile("" : "+v"(nlv));
+#pragma unroll
+        for (int i = 0; i < NT; ++i) tile_pos(i, nlv & (SW - 1), (nlv >> a.lsw) & (SH - 1), nlv >> (a.lsw + a.lsh));
+    }
     DVF_STAMP(a, t_loop1);
     // (tuning build) the account is written when the wave leaves the kernel: epilogue stores issued AND completed
     auto stamp_out = [&]() {
@@ -627,6 +670,27 @@ __global__ __launch_bounds__(PIPE_THREADS_4P) void conv_pipe_kernel(const PipeAr
 // conv_pipe_inst*.hip units (explicit specialisations), declared here for conv.hip.
 template <int MT, int NT, int WM>
 int launch_pipe_family(const PipeArgs &a, int CKH, int TBU, dim3 grid, size_t lds, hipStream_t st, int threads);
+// ... and its low-register form (NPMAX = PIPE_LR_NPI; conv_pipe_inst_d.hip, conv_pipe_inst_e.hip): the instantiations pipe_has_lr() names
+template <int MT, int NT, int WM>
+int launch_pipe_family_lr(const PipeArgs &a, int CKH, int TBU, dim3 grid, size_t lds, hipStream_t st, int threads);
+
+// The low-register form: the producers' tables hold PIPE_LR_NPI pieces instead of PIPE_MAXNPI, the MFMA waves keep less alive
+// across the chunk loop (LR in the kernel) and the kernel is compiled for four waves per SIMD (<= 128 VGPRs; hipcc reaches
+// 58-121 without scratch), so that two blocks share a CU when the plan's LDS fits twice: the second block uses the matrix
+// pipe while the first one stands at a chunk barrier or in its prologue / epilogue.  Built for the 32-channel plans and the
+// 64-channel ones of one tile per wave (profiles/pipe_two_blocks.txt: the register table, and 9-26 % per launch on grids
+// of more than one block per CU, 6-wave and 8-wave blocks alike); not for the two instantiations that would spill, the
+// WM = 2 families (small maps: a block has its CU anyway) and blocked accumulation (plans that own a CU).
+constexpr int PIPE_LR_NPI = 12;
+// ... and the LDS a plan may use: half of a CU's 160 KiB exactly (the planner's own budget for grids of several blocks per CU is
+// 76 KiB; the heaviest such plans of the product steps use 75.1 KiB, so whether two blocks of the full 80 KiB plus the allocation
+// granularity still share a CU is not measured -- if they do not, such a launch runs one block per CU as the wide form does)
+constexpr size_t PIPE_LR_LDS = 80 * 1024;
+constexpr bool pipe_has_lr(int MT, int NT, int WM, int CKH, int TBU) {
+    if (WM != 1) return false;
+    if (MT == 2) return NT == 1;
+    return !(NT == 2 && CKH == 4 && TBU >= 5);      // (these two keep 2 / 226 VGPRs in scratch at 128)
+}
 
 // blocks that use more than 64 KiB of LDS need the opt-in attribute (set once per kernel)
 // (BLK = 1, the instantiation with the second accumulator set, exists for the shapes the product banks: 64-channel waves,
@@ -641,50 +705,62 @@ constexpr bool pipe_has_blk() {
 #endif
 }
 
-template <int MT, int NT, int WM, int CKH, int TBU, int BLK>
+// (one `big_lds` per instantiation of this function, that is per kernel: the two table sizes are two kernels)
+template <int MT, int NT, int WM, int CKH, int TBU, int BLK, int NPMAX = PIPE_MAXNPI>
 inline int launch_pipe_blk(const PipeArgs &a, dim3 grid, size_t lds, hipStream_t st, int threads) {
     static bool big_lds = false;
     if (lds > 64 * 1024 && !big_lds) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_pipe_kernel<MT, NT, WM, CKH, TBU, BLK>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_pipe_kernel<MT, NT, WM, CKH, TBU, BLK, NPMAX>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return DVF_ERR_LAUNCH;
         big_lds = true;
     }
-    conv_pipe_kernel<MT, NT, WM, CKH, TBU, BLK><<<grid, threads, lds, st>>>(a);
+    conv_pipe_kernel<MT, NT, WM, CKH, TBU, BLK, NPMAX><<<grid, threads, lds, st>>>(a);
     return hipGetLastError() == hipSuccess ? DVF_OK : DVF_ERR_LAUNCH;
 }
 
-template <int MT, int NT, int WM, int CKH, int TBU>
+template <int MT, int NT, int WM, int CKH, int TBU, bool LR>
 inline int launch_pipe_one(const PipeArgs &a, dim3 grid, size_t lds, hipStream_t st, int threads) {
-    if (a.blk) {
-        if constexpr (pipe_has_blk<MT, NT, WM, CKH, TBU>()) return launch_pipe_blk<MT, NT, WM, CKH, TBU, 1>(a, grid, lds, st, threads);
-        else return DVF_ERR_UNSUPPORTED;
+    if constexpr (LR) {
+        if constexpr (pipe_has_lr(MT, NT, WM, CKH, TBU)) {
+            if (a.blk || lds > PIPE_LR_LDS) return DVF_ERR_UNSUPPORTED;
+            return launch_pipe_blk<MT, NT, WM, CKH, TBU, 0, PIPE_LR_NPI>(a, grid, lds, st, threads);
+        } else {
+            return DVF_ERR_UNSUPPORTED;
+        }
+    } else {
+        if (a.blk) {
+            if constexpr (pipe_has_blk<MT, NT, WM, CKH, TBU>()) return launch_pipe_blk<MT, NT, WM, CKH, TBU, 1>(a, grid, lds, st, threads);
+            else return DVF_ERR_UNSUPPORTED;
+        }
+        return launch_pipe_blk<MT, NT, WM, CKH, TBU, 0>(a, grid, lds, st, threads);
     }
-    return launch_pipe_blk<MT, NT, WM, CKH, TBU, 0>(a, grid, lds, st, threads);
 }
 
-template <int MT, int NT, int WM, int CKH>
+template <int MT, int NT, int WM, int CKH, bool LR>
 inline int launch_pipe_tbu(const PipeArgs &a, int TBU, dim3 grid, size_t lds, hipStream_t st, int threads) {
     switch (TBU) {
-        case 1: return launch_pipe_one<MT, NT, WM, CKH, 1>(a, grid, lds, st, threads);
-        case 2: return launch_pipe_one<MT, NT, WM, CKH, 2>(a, grid, lds, st, threads);
-        case 3: return launch_pipe_one<MT, NT, WM, CKH, 3>(a, grid, lds, st, threads);
-        case 4: return launch_pipe_one<MT, NT, WM, CKH, 4>(a, grid, lds, st, threads);
-        case 5: if constexpr (CKH <= 4 && WM == 1) return launch_pipe_one<MT, NT, WM, CKH, 5>(a, grid, lds, st, threads); else return DVF_ERR_UNSUPPORTED;
-        case 7: if constexpr (CKH <= 4 && WM == 1) return launch_pipe_one<MT, NT, WM, CKH, 7>(a, grid, lds, st, threads); else return DVF_ERR_UNSUPPORTED;
+        case 1: return launch_pipe_one<MT, NT, WM, CKH, 1, LR>(a, grid, lds, st, threads);
+        case 2: return launch_pipe_one<MT, NT, WM, CKH, 2, LR>(a, grid, lds, st, threads);
+        case 3: return launch_pipe_one<MT, NT, WM, CKH, 3, LR>(a, grid, lds, st, threads);
+        case 4: return launch_pipe_one<MT, NT, WM, CKH, 4, LR>(a, grid, lds, st, threads);
+        case 5: if constexpr (CKH <= 4 && WM == 1) return launch_pipe_one<MT, NT, WM, CKH, 5, LR>(a, grid, lds, st, threads); else return DVF_ERR_UNSUPPORTED;
+        case 7: if constexpr (CKH <= 4 && WM == 1) return launch_pipe_one<MT, NT, WM, CKH, 7, LR>(a, grid, lds, st, threads); else return DVF_ERR_UNSUPPORTED;
         default: return DVF_ERR_UNSUPPORTED;
     }
 }
 
-#define DVF_PIPE_FAMILY(MT, NT, WM)                                                                              \
+#define DVF_PIPE_FAMILY_(NAME, LR, MT, NT, WM)                                                                   \
     template <>                                                                                                  \
-    int launch_pipe_family<MT, NT, WM>(const PipeArgs &a, int CKH, int TBU, dim3 grid, size_t lds, hipStream_t st, int threads) { \
+    int NAME<MT, NT, WM>(const PipeArgs &a, int CKH, int TBU, dim3 grid, size_t lds, hipStream_t st, int threads) { \
         switch (CKH) {                                                                                           \
-            case 2: return launch_pipe_tbu<MT, NT, WM, 2>(a, TBU, grid, lds, st, threads);                                \
-            case 4: return launch_pipe_tbu<MT, NT, WM, 4>(a, TBU, grid, lds, st, threads);                                \
-            case 8: return launch_pipe_tbu<MT, NT, WM, 8>(a, TBU, grid, lds, st, threads);                                \
+            case 2: return launch_pipe_tbu<MT, NT, WM, 2, LR>(a, TBU, grid, lds, st, threads);                   \
+            case 4: return launch_pipe_tbu<MT, NT, WM, 4, LR>(a, TBU, grid, lds, st, threads);                   \
+            case 8: return launch_pipe_tbu<MT, NT, WM, 8, LR>(a, TBU, grid, lds, st, threads);                   \
             default: return DVF_ERR_UNSUPPORTED;                                                                 \
         }                                                                                                        \
     }
+#define DVF_PIPE_FAMILY(MT, NT, WM) DVF_PIPE_FAMILY_(launch_pipe_family, false, MT, NT, WM)
+#define DVF_PIPE_FAMILY_LR(MT, NT, WM) DVF_PIPE_FAMILY_(launch_pipe_family_lr, true, MT, NT, WM)
 
 }  // namespace dvfp

@@ -295,6 +295,8 @@ int g_stamp_blocks = 0;
 struct PipePlan {
     PipeArgs a;              // geometry and tiling; the operands are set at launch
     int MT, NT, WM, CKH, TBU, threads;
+    int npi;                 // patch pieces per channel (the largest of the classes)
+    int lr;                  // the low-register form of the kernel (conv_pipe.h: PIPE_LR_NPI): two blocks share a CU
     size_t lds;
     dim3 grid;
     int64_t packed_floats;   // the op's share of the packed-weight buffer
@@ -421,13 +423,14 @@ int plan_pipe(const ConvOp &op, PipePlan &pl) {
     static const int big_lds_kb = dvf_tune("DVF_PIPE_BIGLDS_KB") ? atoi(dvf_tune("DVF_PIPE_BIGLDS_KB")) : 150;   // tuning knob
     // LDS budget: a grid of at most one block per CU may take (nearly) the whole 160 KiB; otherwise leave room for two
     const size_t PIPE_LDS_BUDGET = (nblk * KS0 <= 256 ? big_lds_kb : 76) * 1024;
-    struct Depth { int ok, CK, NST, PSRmax; size_t lds; };
+    struct Depth { int ok, CK, NST, PSRmax; size_t lds; int NPImax; };
     auto depth_for = [&](int x4) {
-        Depth d{0, 0, 3, 0, 0};
+        Depth d{0, 0, 3, 0, 0, 0};
         for (int i = 0; i < ncls; ++i) {
             const PipeGeo g = pipe_geo(a.BH, a.BW, a.BN, a.IS, cls[i].TA, TBU, SW, SH, x4, cls[i].bx);
             if (g.NPI > PIPE_MAXNPI) return d;
             d.PSRmax = g.PSR > d.PSRmax ? g.PSR : d.PSRmax;
+            d.NPImax = g.NPI > d.NPImax ? g.NPI : d.NPImax;
         }
         auto lds_bytes = [&](int CK) { return ((size_t)d.NST * (slab(CK, TAmax) + (size_t)CK * d.PSRmax) + MB) * 4; };
         // chunk depth: largest CK in {16,8,4} whose stages fit the LDS budget
@@ -450,7 +453,7 @@ int plan_pipe(const ConvOp &op, PipePlan &pl) {
     };
     int want_x4 = (a.IW % 4 == 0 && (a.BW * a.IS) % 4 == 0) ? 1 : 0;
     if (const char *e = dvf_tune("DVF_PIPE_X4")) want_x4 = want_x4 && atoi(e) != 0;    // tuning knob: 0 = 4-byte lanes everywhere
-    const Depth d1 = depth_for(0), d4 = want_x4 ? depth_for(1) : Depth{0, 0, 3, 0, 0};
+    const Depth d1 = depth_for(0), d4 = want_x4 ? depth_for(1) : Depth{0, 0, 3, 0, 0, 0};
     static const bool x4_force = dvf_tune("DVF_PIPE_X4") && atoi(dvf_tune("DVF_PIPE_X4")) == 2;           // tuning: 2 = whenever legal
     const bool use4 = d4.ok && (!d1.ok || x4_force || (d4.CK >= d1.CK && d4.NST >= d1.NST));
     const Depth dd = use4 ? d4 : d1;
@@ -512,15 +515,31 @@ int plan_pipe(const ConvOp &op, PipePlan &pl) {
     {
         const int64_t nblocks_total = (int64_t)pl.grid.x * pl.grid.y * pl.grid.z;
         static const bool no4p = dvf_tune("DVF_PIPE_NO4P") != nullptr;
-        // (32-channel MFMA waves need <= 128 VGPRs: two 8-wave blocks still fit a CU)
+        // (32-channel plans: four producers also on grids of several blocks per CU -- measured; two such blocks share a CU only
+        // in the low-register form below)
         static const int mt1_4p = dvf_tune("DVF_PIPE_MT1_4P") ? atoi(dvf_tune("DVF_PIPE_MT1_4P")) : 1;      // tuning knob
         pl.threads = (!no4p && (pl.lds > 76 * 1024 || nblocks_total <= 256 || (MT == 1 && mt1_4p))) ? dvfp::PIPE_THREADS_4P : dvfp::PIPE_THREADS;
+        // At 141-167 VGPRs (three waves per SIMD) a block keeps other blocks off its CU whatever its LDS.  Where the grid has
+        // more blocks than CUs, the plan's LDS fits a CU twice and its patch fits the small piece table, the launch takes the
+        // low-register form of the kernel (conv_pipe.h): two blocks share a CU.  The plan is untouched -- same tile, CK, KS, NST,
+        // threads -- and so are the results, bit for bit.  (Grids of at most one block per CU were not measured: they stay.)
+        pl.npi = dd.NPImax;
+        const bool lr_fits = !a.blk && dd.NPImax <= dvfp::PIPE_LR_NPI && pl.lds <= dvfp::PIPE_LR_LDS &&
+                             dvfp::pipe_has_lr(MT, NT, WM, CK / 2, TBU);
+        pl.lr = lr_fits && nblocks_total > 256;
+        if (const char *e = dvf_tune("DVF_PIPE_LR")) pl.lr = lr_fits && atoi(e) != 0;     // tuning: 0 never, 1 wherever it fits
     }
     return DVF_OK;
 }
 
 int launch_pipe(const PipeArgs &a, const PipePlan &pl, hipStream_t st) {
     using dvfp::launch_pipe_family;
+    if (pl.lr) {
+        if (pl.WM != 1) return DVF_ERR_UNSUPPORTED;
+        if (pl.MT == 2) return dvfp::launch_pipe_family_lr<2, 1, 1>(a, pl.CKH, pl.TBU, pl.grid, pl.lds, st, pl.threads);
+        return pl.NT == 2 ? dvfp::launch_pipe_family_lr<1, 2, 1>(a, pl.CKH, pl.TBU, pl.grid, pl.lds, st, pl.threads)
+                          : dvfp::launch_pipe_family_lr<1, 1, 1>(a, pl.CKH, pl.TBU, pl.grid, pl.lds, st, pl.threads);
+    }
     if (pl.WM == 2) {
         if (pl.NT != 1) return DVF_ERR_UNSUPPORTED;
         return pl.MT == 2 ? launch_pipe_family<2, 1, 2>(a, pl.CKH, pl.TBU, pl.grid, pl.lds, st, pl.threads)
@@ -560,7 +579,7 @@ int run_pipe(const ConvOp &op, const PipePlan &pl, const ConvIO &io, const float
         }
     }
 #endif
-    dvf_plan_note(DVF_K_PIPE, pl.MT, pl.NT, pl.WM, 2 * pl.CKH, pl.TBU, a.KS, a.BN, a.NST, pl.threads, (int)pl.lds, mode | (a.ncls << 4) | (a.x4 << 8) | ((a.blk ? 1 : 0) << 9));
+    dvf_plan_note(DVF_K_PIPE, pl.MT, pl.NT, pl.WM, 2 * pl.CKH, pl.TBU, a.KS, a.BN, a.NST, pl.threads, (int)pl.lds, mode | (a.ncls << 4) | (a.x4 << 8) | ((a.blk ? 1 : 0) << 9) | (pl.lr << 10) | (pl.npi << 11));
     if (dvf_tune("DVF_PIPE_DEBUG"))
         fprintf(stderr, "[pipe] M %d chunks %d N %d out %dx%d cls %d | MT %d NT %d WM %d CK %d TBU %d KS %d BN %d tile %dx%d "
                 "(sub %dx%d) grid %ux%ux%u lds %zu x%d mode %d\n", a.M, a.NCH, a.N, a.OH, a.OW, a.ncls, pl.MT, pl.NT, pl.WM,
