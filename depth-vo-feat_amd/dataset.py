@@ -152,3 +152,105 @@ def depth_validation_set(root, img_height, img_width):
     """The depth validation set under ``root`` (see ``DepthValidationSet``); ``.loader(batch_size)`` batches it by
     ground-truth size."""
     return DepthValidationSet(root, img_height, img_width)
+
+
+class KittiRawDepthSet(data.Dataset):
+    """Frames of a KITTI raw tree with their LiDAR sweep and calibration, for ``dvf.validation.validate_depth`` and
+    ``export_depth_tree``: the ground truth is built from the sweep on the device (``dvf.velodyne.depth_maps``), nothing is
+    projected here.  A line of ``split_file`` is ``<date>/<drive>/image_0<cam>/data/<id>.png ...`` (an Eigen split list): the
+    first field names the frame and later fields are ignored, as in the reference's read_file_data
+    (tools/eval_depth_utils.py:79-109); the camera directory of the line is replaced by ``cam``'s.  The sweep is
+    ``<date>/<drive>/velodyne_points/data/<id>.bin`` (raw float32 quadruples) and the calibration comes from
+    ``dvf.velodyne.find_calib_dir``.  A listed frame whose image is absent is reported (``<path> missing``) and skipped, as the
+    reference does; an absent sweep or calibration file of a present image raises with the path.
+
+    A sample is (frame [3,img_height,img_width] float32 through the same ``imread`` / ``imresize`` as ``DepthValidationSet``,
+    points [N,4] float32, proj [3,4] float64).  ``shapes`` lists every sample's ground-truth size (Hg, Wg) = the size of the
+    ORIGINAL image, read from the file header without decoding; ``stems`` its ``<drive>_<id>``."""
+
+    def __init__(self, root, split_file, img_height, img_width, cam=2):
+        from PIL import Image
+        from dvf.velodyne import CAMS, find_calib_dir, velo_to_image
+        if cam not in CAMS:
+            raise ValueError(f"KittiRawDepthSet: cam must be one of {CAMS}, got {cam!r}")
+        self.root, self.height, self.width, self.cam = root, img_height, img_width, cam
+        self.images, self.sweeps, self.projs, self.shapes, self.stems, self.missing = [], [], [], [], [], []
+        calib = {}
+        with open(split_file) as f:
+            lines = [line.split()[0] for line in f if line.strip()]
+        for name in lines:
+            parts = name.split("/")
+            if len(parts) != 5:
+                raise ValueError(f"{split_file}: expected <date>/<drive>/image_0<cam>/data/<id>.png, got {name!r}")
+            date, drive, frame_id = parts[0], parts[1], os.path.splitext(parts[4])[0]
+            image = os.path.join(root, date, drive, f"image_0{cam}", "data", parts[4])
+            if not os.path.isfile(image):
+                print(f"{image} missing", flush=True)
+                self.missing.append(image)
+                continue
+            sweep = os.path.join(root, date, drive, "velodyne_points", "data", frame_id + ".bin")
+            if not os.path.isfile(sweep):
+                raise FileNotFoundError(f"{sweep}: no LiDAR sweep for {image}")
+            calib_dir = find_calib_dir(root, date, drive)
+            if calib_dir not in calib:
+                calib[calib_dir] = velo_to_image(calib_dir, cam)
+            with Image.open(image) as im:                              # (the header only: nothing is decoded)
+                wg, hg = im.size
+            self.images.append(image)
+            self.sweeps.append(sweep)
+            self.projs.append(calib[calib_dir])
+            self.shapes.append((hg, wg))
+            self.stems.append(f"{drive}_{frame_id}")
+
+    def frame(self, index):
+        img = imresize(imread(self.images[index]).astype(np.float32), (self.height, self.width)).astype(np.float32)
+        return torch.from_numpy(np.ascontiguousarray(np.transpose(img, (2, 0, 1))))
+
+    def sweep(self, index):
+        """(points [N,4] float32, proj [3,4] float64) of a sample."""
+        points = np.fromfile(self.sweeps[index], dtype=np.float32)
+        if points.size % 4:
+            raise ValueError(f"{self.sweeps[index]}: {points.size} floats are no whole number of (x, y, z, reflectance) points")
+        return torch.from_numpy(points.reshape(-1, 4)), torch.from_numpy(np.ascontiguousarray(self.projs[index], dtype=np.float64))
+
+    def __getitem__(self, index):
+        return (self.frame(index),) + self.sweep(index)
+
+    def __len__(self):
+        return len(self.images)
+
+    batches = DepthValidationSet.batches
+
+    def collate(self, indices, frames=True):
+        """One batch of ``batches``: (frames [B,3,h,w], points [total,4], offsets [B+1] int32, proj [B,3,4] float64, (Hg, Wg)),
+        the points of the B sweeps back to back and frame b owning points offsets[b] .. offsets[b+1]-1.  ``frames=False``
+        decodes no image and puts None first."""
+        sweeps = [self.sweep(i) for i in indices]
+        offsets = torch.tensor(np.concatenate([[0], np.cumsum([p.shape[0] for p, _ in sweeps])]), dtype=torch.int32)
+        return (torch.stack([self.frame(i) for i in indices]) if frames else None, torch.cat([p for p, _ in sweeps]), offsets,
+                torch.stack([m for _, m in sweeps]), tuple(self.shapes[indices[0]]))
+
+    def loader(self, batch_size, num_workers=0):
+        """A DataLoader over the collated batches of ``batches(batch_size)``; ``.dataset.source`` is this set."""
+        return data.DataLoader(_RawDepthBatches(self, self.batches(batch_size)), batch_size=None, shuffle=False,
+                               num_workers=num_workers)
+
+
+class _RawDepthBatches(data.Dataset):
+    """Item i = the collated batch i of a KittiRawDepthSet (the ground-truth size of a batch is the set's knowledge, not
+    the samples')."""
+
+    def __init__(self, source, batches):
+        self.source, self.batches = source, batches
+
+    def __getitem__(self, index):
+        return self.source.collate(self.batches[index])
+
+    def __len__(self):
+        return len(self.batches)
+
+
+def kitti_raw_depth_set(root, split_file, img_height, img_width, cam=2):
+    """The frames of ``split_file`` under the KITTI raw tree ``root`` (see ``KittiRawDepthSet``); ``.loader(batch_size)``
+    batches them by ground-truth size and collates the sweeps."""
+    return KittiRawDepthSet(root, split_file, img_height, img_width, cam)

@@ -10,7 +10,11 @@ Run as a script (``python depth_eval.py --pretrained-disp CKPT --val-depth-root 
 through dvf.validation.validate_depth / dvf.metrics.depth_metrics instead.  The two differ in one documented place: ``evaluate``
 uses numpy's median, the MEAN OF THE TWO middle elements for an even count, while the device path takes torch.median's lower
 median as the reference's training-side compute_errors does (loss_functions_sfm.py:104); the mean-of-two form is not
-reproduced on the device.  The device path also clamps once, before scaling, unless asked to reclamp."""
+reproduced on the device.  The device path also clamps once, before scaling, unless asked to reclamp.
+
+With ``--kitti-raw-root DIR --split FILE`` instead of ``--val-depth-root`` the ground truth is built on the GPU from the LiDAR
+sweeps of a KITTI raw tree (dvf.velodyne.depth_maps: the reference's generate_depth_map, tools/eval_depth_utils.py:172-224,
+whose module is Python 2 and imports cv2 as well), and ``--export-depth-root OUT`` writes it as a tree --val-depth-root reads."""
 import numpy as np
 
 
@@ -56,31 +60,56 @@ def evaluate(gt_depths, pred_depths, min_depth=1e-3, max_depth=80.0, garg_crop=T
 
 
 def main(argv=None):
-    """Evaluate a depth checkpoint against a depth validation tree on the GPU and print the seven Eigen metrics plus
-    abs_diff (the line train.py --val-depth-root prints after every epoch)."""
+    """Evaluate a depth checkpoint against a depth validation tree, or against the LiDAR sweeps of a KITTI raw tree, on the GPU
+    and print the seven Eigen metrics plus abs_diff (the line train.py --val-depth-root prints after every epoch)."""
     import argparse
     import torch
     from DispNetS import DispNetS
-    from dataset import depth_validation_set
+    from dataset import depth_validation_set, kitti_raw_depth_set
     from dvf import cli, validation
     parser = argparse.ArgumentParser(description="Depth evaluation against ground truth on MI355X",
                                      formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     parser.add_argument("--pretrained-disp", required=True, metavar="PATH", help="DispNetS checkpoint (best_depth_checkpoint.pth.tar)")
-    parser.add_argument("--val-depth-root", required=True, metavar="DIR",
-                        help="val.txt, image/<stem>.png|jpg, depth/<stem>.npy in metres (0 = no measurement)")
+    parser.add_argument("--val-depth-root", default=None, metavar="DIR",
+                        help="val.txt, image/<stem>.png|jpg, depth/<stem>.npy in metres (0 = no measurement); "
+                             "this or --kitti-raw-root is required")
+    parser.add_argument("--kitti-raw-root", default=None, metavar="DIR",
+                        help="KITTI raw tree (<date>/<drive>/image_0<cam>/data, velodyne_points/data, the calibration files in "
+                             "<date>/ or <date>/<drive>/calib/): the ground truth is built from the LiDAR sweeps on the GPU; needs --split")
+    parser.add_argument("--split", default=None, metavar="FILE",
+                        help="with --kitti-raw-root: the frames to evaluate, one <date>/<drive>/image_0<cam>/data/<id>.png per line "
+                             "(an Eigen split list; later fields of a line are ignored)")
+    parser.add_argument("--cam", type=int, choices=[2, 3], default=2, help="with --kitti-raw-root: the colour camera, 2 = left, 3 = right")
+    parser.add_argument("--velodyne-depth", action="store_true",
+                        help="with --kitti-raw-root: the ground truth is the LiDAR's forward distance instead of the camera depth")
+    parser.add_argument("--export-depth-root", default=None, metavar="OUT",
+                        help="with --kitti-raw-root: also write the ground truth as a tree that --val-depth-root reads "
+                             "(val.txt, image/<stem>.png copied, depth/<stem>.npy)")
     parser.add_argument("--height", type=int, default=256)
     parser.add_argument("--width", type=int, default=832)
     parser.add_argument("-b", "--batch-size", type=int, default=4)
     parser.add_argument("--no-crop", action="store_true", help="all pixels instead of the Garg crop")
     parser.add_argument("--no-median-scaling", action="store_true", help="compare the prediction as it is")
     args = parser.parse_args(argv)
+    if (args.val_depth_root is None) == (args.kitti_raw_root is None):
+        parser.error("exactly one of --val-depth-root and --kitti-raw-root is required")
+    if args.kitti_raw_root is not None and args.split is None:
+        parser.error("--kitti-raw-root needs --split")
+    if args.kitti_raw_root is None and (args.split is not None or args.velodyne_depth or args.export_depth_root is not None):
+        parser.error("--split, --velodyne-depth and --export-depth-root need --kitti-raw-root")
     cli.require_gpu()
     device = torch.device("cuda", 0)
     net = DispNetS()
     cli.load_pretrained(net, args.pretrained_disp)
     net.to(device)
-    loader = depth_validation_set(args.val_depth_root, args.height, args.width).loader(args.batch_size)
-    metrics = validation.validate_depth(net, loader, device, crop=not args.no_crop, median_scaling=not args.no_median_scaling)
+    if args.kitti_raw_root is not None:
+        loader = kitti_raw_depth_set(args.kitti_raw_root, args.split, args.height, args.width, cam=args.cam).loader(args.batch_size)
+        if args.export_depth_root is not None:
+            validation.export_depth_tree(loader, args.export_depth_root, device, velodyne_depth=args.velodyne_depth)
+    else:
+        loader = depth_validation_set(args.val_depth_root, args.height, args.width).loader(args.batch_size)
+    metrics = validation.validate_depth(net, loader, device, crop=not args.no_crop, median_scaling=not args.no_median_scaling,
+                                        velodyne_depth=args.velodyne_depth)
     print(validation.format_depth_metrics(metrics), flush=True)
     return metrics
 

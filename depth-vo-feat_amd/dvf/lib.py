@@ -36,6 +36,7 @@ ROT_QUAT, PAD_BORDER, ALIGN_CORNERS, POSE_SE3, PIXEL_COORDS, CAFFE_ABSLOSS = 1, 
 ACT_NONE, ACT_RELU, ACT_SIGMOID_AFFINE = 0, 1, 2
 MAX_VIEWS, MAX_SEGS = 4, 5
 DM_MEDIAN_SCALE, DM_RECLAMP = 1, 2
+VD_VELODYNE_DEPTH = 1
 
 # name -> (restype, argtypes); kept in one table so tests can check every declared symbol is exported
 SIGNATURES = {
@@ -103,6 +104,7 @@ SIGNATURES = {
     "dvf_adam_step": (c_i, [c_fp] * 4 + [c_i64, c_fp, c_i] + [c_f] * 5 + [c_fp]),
     "dvf_depth_metrics_ws_floats": (c_i64, [c_i] * 3),
     "dvf_depth_metrics": (c_i, [c_fp] * 4 + [c_i64] + [c_i] * 7 + [c_f] * 4 + [c_u32, c_fp]),
+    "dvf_velodyne_depth": (c_i, [c_fp] * 4 + [c_i] * 4 + [c_u32, c_fp]),
     "dvf_pose_chain": (c_i, [c_fp, c_ip, c_i, c_fp, c_fp]),
     "dvf_odometry_errors_ws_doubles": (c_i64, [c_i]),
     "dvf_odometry_errors": (c_i, [c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_fp, c_i64, c_fp]),
@@ -156,14 +158,15 @@ def stream_raw():
     return torch._C._cuda_getCurrentRawStream(_DEV_INDEX)
 
 
-def dev(t, name="tensor"):
-    """Validate a tensor for the C ABI (cuda, fp32, contiguous) and return its device pointer (an integer; None for None)."""
+def dev(t, name="tensor", dtype=torch.float32):
+    """Validate a tensor for the C ABI (cuda, ``dtype`` = fp32 unless the entry takes another, contiguous) and return its device
+    pointer (an integer; None for None)."""
     if t is None:
         return None
     if not t.is_cuda:
         raise RuntimeError(f"{name}: the HIP path needs a CUDA/HIP tensor, got {t.device}; there is no CPU fallback")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name}: expected float32, got {t.dtype}")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected {str(dtype).replace('torch.', '')}, got {t.dtype}")
     if not t.is_contiguous():
         raise RuntimeError(f"{name}: expected a contiguous tensor")
     return t.data_ptr()

@@ -44,11 +44,23 @@ def format_depth_metrics(metrics):
     return "Depth: " + " ".join(f"{k} {metrics[k]:.9f}" for k in METRICS)
 
 
+def raw_ground_truth(batch, device, velodyne_depth=False):
+    """(frames, depth [B,Hg,Wg] on the device) of one batch of dataset.kitti_raw_depth_set(...).loader(b) = (frames, points
+    [total,4], offsets [B+1] int32, proj [B,3,4] fp64, (Hg, Wg)): the LiDAR sweeps projected by dvf.velodyne.depth_maps."""
+    from .velodyne import depth_maps
+    img, points, offsets, proj, (hg, wg) = batch
+    gt = depth_maps(points.float().to(device).contiguous(), offsets.to(device=device, dtype=torch.int32).contiguous(),
+                    proj.to(device=device, dtype=torch.float64).contiguous(), int(hg), int(wg), velodyne_depth=velodyne_depth)
+    return img, gt
+
+
 @torch.no_grad()
-def validate_depth(disp_net, loader, device, crop=True, median_scaling=True):
+def validate_depth(disp_net, loader, device, crop=True, median_scaling=True, velodyne_depth=False):
     """Depth validation against ground truth: the mean over the validation images (those with a valid pixel) of the eight
     metrics of dvf.metrics.depth_metrics, as a dict.  ``loader`` yields (frames [B,3,h,w], depth [B,Hg,Wg]) batches
-    (dataset.depth_validation_set(...).loader(b)).  The network runs in eval mode; its finest disparity is brought to the
+    (dataset.depth_validation_set(...).loader(b)), or the five-part batches of dataset.kitti_raw_depth_set(...).loader(b),
+    whose ground truth is then built on the device from the LiDAR sweeps (raw_ground_truth; ``velodyne_depth`` applies to
+    these only).  The network runs in eval mode; its finest disparity is brought to the
     ground truth's size bilinearly (dvf_resize_bilinear_fwd, scale h/Hg, w/Wg) and inverted, then one depth_metrics call per
     batch; sums and the image count accumulate on the device (dvf.metrics.sum_rows / mean_rows, the two halves of
     reduce_rows) and the pass synchronises once, at its end."""
@@ -57,7 +69,8 @@ def validate_depth(disp_net, loader, device, crop=True, median_scaling=True):
     total = torch.zeros(len(METRICS), device=device)
     count = torch.zeros((), device=device)
     with eval_mode(disp_net):
-        for img, gt in loader:
+        for batch in loader:
+            img, gt = batch if len(batch) == 2 else raw_ground_truth(batch, device, velodyne_depth)
             img, gt = img.float().to(device).contiguous(), gt.float().to(device).contiguous()
             disp = disp_net(img)
             disp = (disp[0] if type(disp) in (list, tuple) else disp).contiguous()
@@ -72,6 +85,34 @@ def validate_depth(disp_net, loader, device, crop=True, median_scaling=True):
             total += batch_total
             count += batch_count
     return dict(zip(METRICS, mean_rows(total, count).tolist()))          # the pass's one synchronisation
+
+
+def export_depth_tree(loader_or_set, out_root, device="cuda", velodyne_depth=False, batch_size=4):
+    """Write the depth validation tree of a KITTI raw set (dataset.kitti_raw_depth_set(...) or its ``.loader(b)``) under
+    ``out_root``: ``val.txt`` (one stem per line, ``<drive>_<id>``), ``image/<stem>.png`` (the original file, copied, not
+    re-encoded) and ``depth/<stem>.npy`` (the map dvf.velodyne.depth_maps builds on the device, float32 [Hg,Wg] in metres, 0 =
+    no measurement).  This is the layout dataset.depth_validation_set / --val-depth-root reads.  Returns the stems.  A loader
+    brings its own batches; a set is walked in batches of ``batch_size``.  No frame is decoded here.  The export is a pass of
+    its own: depth_eval.py --export-depth-root reads and projects every sweep once here and once more in validate_depth."""
+    import shutil
+    import numpy as np
+    if isinstance(loader_or_set, torch.utils.data.DataLoader):           # set.loader(b): its dataset lists the set's batches
+        source, batches = loader_or_set.dataset.source, loader_or_set.dataset.batches
+    else:
+        source, batches = loader_or_set, loader_or_set.batches(batch_size)
+    if len(set(source.stems)) != len(source.stems):
+        raise ValueError("export_depth_tree: the split lists a frame twice")
+    for sub in ("image", "depth"):
+        os.makedirs(os.path.join(out_root, sub), exist_ok=True)
+    for indices in batches:
+        _, gt = raw_ground_truth(source.collate(indices, frames=False), device, velodyne_depth)
+        for i, depth in zip(indices, gt.cpu().numpy()):
+            stem = source.stems[i]
+            shutil.copyfile(source.images[i], os.path.join(out_root, "image", stem + os.path.splitext(source.images[i])[1]))
+            np.save(os.path.join(out_root, "depth", stem + ".npy"), depth)
+    with open(os.path.join(out_root, "val.txt"), "w") as f:
+        f.write("".join(stem + "\n" for stem in source.stems))
+    return list(source.stems)
 
 
 def pose_epoch_lines(loss, is_best):

@@ -8,7 +8,8 @@ instead of nn.DataParallel.  ``validate()`` (odometry L1 against the ground-trut
 train.py:220-247) runs after every epoch when --val-root points at a KITTI-odometry tree (sequences/<seq>/image_2,
 poses/<seq>.txt) and then decides the best checkpoint like the reference; otherwise the best training loss does.
 With --val-depth-root the depth network is validated against ground-truth depth after every epoch as well (Eigen metrics,
-computed on the GPU) and best_depth_checkpoint.pth.tar follows the best abs_rel.  With --val-odometry (and --val-root) the pose
+computed on the GPU) and best_depth_checkpoint.pth.tar follows the best abs_rel; --val-kitti-raw-root with --val-split does
+the same against ground truth built on the GPU from the LiDAR sweeps of a KITTI raw tree.  With --val-odometry (and --val-root) the pose
 network's outputs over each test sequence are chained into a trajectory after every epoch and scored with the KITTI odometry
 errors, on the GPU as well; best_odometry_checkpoint.pth.tar follows the best t_err.  --val-odometry-align MODE first brings
 every trajectory onto its ground truth (scale, 6dof, 7dof: a monocular network's scale is arbitrary), so that t_err is the
@@ -61,6 +62,12 @@ parser.add_argument("--val-depth-root", default=None, metavar="DIR",
                     help="depth validation tree (val.txt, image/<stem>.png|jpg, depth/<stem>.npy in metres, 0 = no measurement): "
                          "after every epoch rank 0 prints the Eigen depth metrics of the depth network against it "
                          "(dvf.validation.validate_depth) and best_depth_checkpoint.pth.tar is saved on the best abs_rel")
+parser.add_argument("--val-kitti-raw-root", default=None, metavar="DIR",
+                    help="in place of --val-depth-root: a KITTI raw tree; the ground truth of the frames of --val-split is built "
+                         "from their LiDAR sweeps on the GPU (dvf.velodyne.depth_maps), same Depth line and checkpoint rule")
+parser.add_argument("--val-split", default=None, metavar="FILE",
+                    help="needs --val-kitti-raw-root: one <date>/<drive>/image_0<cam>/data/<id>.png per line (an Eigen split list)")
+parser.add_argument("--val-cam", type=int, choices=[2, 3], default=2, help="with --val-kitti-raw-root: the colour camera")
 parser.add_argument("--val-odometry", action="store_true",
                     help="needs --val-root: after every epoch rank 0 also chains the pose network's output over each of "
                          "--test-sequences into a trajectory and prints its KITTI odometry errors (t_err in %%, r_err in deg / 100 m, "
@@ -82,6 +89,10 @@ def main():
         parser.error("--val-odometry needs --val-root")
     if args.val_odometry_align is not None and not args.val_odometry:
         parser.error("--val-odometry-align needs --val-odometry")
+    if args.val_kitti_raw_root and args.val_depth_root:
+        parser.error("--val-kitti-raw-root and --val-depth-root exclude each other")
+    if bool(args.val_kitti_raw_root) != bool(args.val_split):
+        parser.error("--val-kitti-raw-root and --val-split go together")
     args._rank, args._world, args._device = cli.init_distributed()
     if args.epoch_size:
         args.steps_per_epoch = args.epoch_size
@@ -116,9 +127,11 @@ def main():
         # (ckpts=None: the reference's criterion for best_vo / best_depth, in place of the training loss)
         validators.append(cli.Validator(lambda _: validation.validate(pose_exp_net, val_loader, args._device), float,
                                         validation.pose_epoch_lines, None))
-    if args.val_depth_root and args._rank == 0:
-        from dataset import depth_validation_set
-        depth_loader = depth_validation_set(args.val_depth_root, args.height, args.width).loader(args.batch_size)
+    if (args.val_depth_root or args.val_kitti_raw_root) and args._rank == 0:
+        from dataset import depth_validation_set, kitti_raw_depth_set
+        depth_set = (depth_validation_set(args.val_depth_root, args.height, args.width) if args.val_depth_root else
+                     kitti_raw_depth_set(args.val_kitti_raw_root, args.val_split, args.height, args.width, cam=args.val_cam))
+        depth_loader = depth_set.loader(args.batch_size)
         validators.append(cli.Validator(lambda _: validation.validate_depth(disp_net, depth_loader, args._device),
                                         lambda m: m["abs_rel"], validation.depth_epoch_lines,
                                         [("best_depth_checkpoint.pth.tar", disp_net)]))

@@ -430,6 +430,36 @@ int dvf_depth_metrics(const float *gt, const float *pred, float *out /* [B][12] 
                       int W, int y1, int y2, int x1, int x2, float gt_lo, float gt_hi, float clamp_lo, float clamp_hi,
                       uint32_t flags, void *stream);
 
+/* ---------------------------------------------------------------- depth ground truth from LiDAR sweeps
+ * The sparse depth maps that the Eigen protocol scores against: the reference's generate_depth_map
+ * (tools/eval_depth_utils.py:172-224) for B frames in one call.  points [total][4] fp32 = the raw velodyne quadruples
+ * (forward, left, up, reflectance) of all frames back to back, 16-byte aligned; offsets [B+1] DEVICE ints: frame b owns points
+ * offsets[b] .. offsets[b+1]-1; proj [B][3][4] DEVICE DOUBLES = P_rect_0c * R_rect_00 * Tr_velo_to_cam; depth [B][H][W] fp32 out.
+ * Per frame b and per point (x, y, z, .) of it (the fourth component is ignored and taken as 1):
+ *   kept only if x >= 0                                               (a NaN x is dropped)
+ *   p = proj[b] * (x, y, z, 1) in fp64, the floats converted exactly
+ *   u = rint(p0 / p2) - 1, v = rint(p1 / p2) - 1                      (half to even, as np.round; the -1 is KITTI's MATLAB
+ *                                                                      convention, kept by the reference)
+ *   kept only if u >= 0 && v >= 0 && u < W && v < H                   (NaN and +-inf coordinates, p2 == 0, fail)
+ *   d = (float)p2, or with DVF_VD_VELODYNE_DEPTH d = x                (the reference's vel_depth=True)
+ *   depth[b][v][u] = max(0, min over the kept points that land there of d); a pixel that no point reaches is 0.
+ * The minimum comes first and the clamp second (:216-217): one point of negative camera depth on a pixel makes it "no
+ * measurement".  One departure from the reference: it finds collisions through the key row * (W - 1) + col - 1, which pixel
+ * (r, W-1) shares with pixel (r+1, 0), so one of those two can receive the minimum over both; this entry takes the per-pixel
+ * minimum everywhere.  Columns 0 and W-1 lie outside the Garg crop for W >= 28.
+ * The call overwrites every element of depth, whatever it held.  offsets cannot be checked on the host: the kernel clamps
+ * every frame's range to [0, total] and takes offsets[b+1] < offsets[b] as an empty frame, so a wrong offset can misassign
+ * points but never reads outside points.  Integer atomic minima on the bit patterns in depth itself: no workspace, no
+ * allocation, no synchronisation (graph-capturable), and a minimum does not depend on arrival order: two runs are
+ * bit-identical.
+ * Checked on the host before anything is launched: DVF_ERR_INVALID_ARG for a null pointer (points may be null only when
+ * total == 0), points not 16-byte aligned, B, H or W <= 0, total < 0, B * H * W >= 2^31 or a flag bit other than
+ * DVF_VD_VELODYNE_DEPTH. */
+#define DVF_VD_VELODYNE_DEPTH 1u
+int dvf_velodyne_depth(const float *points /* [total][4] */, const int *offsets /* DEVICE, [B+1] */,
+                       const double *proj /* DEVICE, [B][3][4] */, float *depth /* [B][H][W] out */, int B, int H, int W, int total,
+                       uint32_t flags, void *stream);
+
 /* ---------------------------------------------------------------- odometry evaluation: chained trajectory, KITTI segment errors
  * The device form of odometry_eval.py's se3_cam2world / sequence_errors / overall_error (reference inference.py:63-70,
  * tools/evaluation_tools.py:419-508).  All arithmetic is fp64 and these pointers are DEVICE pointers to DOUBLE data unless
