@@ -284,7 +284,7 @@ int run_gather(const ConvOp &op, const GatherPlan &pl, const ConvIO &io, const f
     else if (pl.NT == 2) rc = launch_gather_ck<1, 2>(a, pl, st);
     else rc = launch_gather_ck<1, 1>(a, pl, st);
     if (rc) return rc;
-    dvf_plan_note(DVF_K_GATHER, pl.MT, pl.NT, 1, 2 * pl.CKH, 0, a.KS, 1, 1, 256, (int)pl.lds, a.out_mode | (a.ncls << 4));
+    dvf_note_gather(pl.MT, pl.NT, 2 * pl.CKH, a.KS, (int)pl.lds, a.out_mode, a.ncls);
     return finish_output(a, pl.reduce_kpar, ws, io.out, st);
 }
 
@@ -530,8 +530,8 @@ int run_wgrad_pipe(const WgradPipePlan &pl, const float *P, const float *const *
     int rc = dvf_wgrad_pipe_launch(w, pl.MT, pl.NTW, pl.nblocks, pl.lds, st, pl.TILE);
     if (rc == DVF_OK && w.ws) rc = dvf_wgrad_pipe_reduce(w, pl.MT, pl.NTW, pl.nblocks, st, pl.TILE);
     if (rc) return rc;
-    dvf_plan_note(DVF_K_WGRAD_PIPE, pl.MT | (pl.TILE << 8), pl.NTW, w.x4 | (w.ws ? 2 : 0), w.CK, w.S, w.NPIq, pl.nblocks, (int)pl.lds,
-                  w.KH * w.KW, w.RSq, w.nseg);
+    dvf_note_wgrad_pipe(pl.MT, pl.TILE, pl.NTW, w.x4, w.ws != nullptr, w.CK, w.S, w.NPIq, pl.nblocks, (int)pl.lds, w.KH * w.KW, w.RSq,
+                        w.nseg);
     if (bias_done) *bias_done = w.bias_col >= 0;
     return DVF_OK;
 }

@@ -514,7 +514,7 @@ int dvf_dconvt_fwd(const dvf_conv_desc *d, const float *in, const float *w, cons
     else DCONVT(16, 4);
 #undef DCONVT
     DVF_LAUNCH_CHECK();
-    dvf_plan_note(DVF_K_DCONVT_FWD, d->C_out, d->KH);
+    dvf_note_head(DVF_K_DCONVT_FWD, d->C_out, d->KH);
     return DVF_OK;
 }
 
@@ -571,7 +571,7 @@ int dvf_head_fwd_segs(const dvf_conv_desc *d, const float *const *in_segs, const
     const int rc = head_fwd_launch(d->C_out, in, w, bias, out, d->C_in, d->N, d->H_in, d->W_in, d->act, d->alpha, d->beta,
                                    d->C_in * 9, 9, 0, nullptr, st);
     if (rc) return rc;
-    dvf_plan_note(DVF_K_HEAD_FWD, d->C_out, nseg);
+    dvf_note_head(DVF_K_HEAD_FWD, d->C_out, nseg);
     return DVF_OK;
 }
 
@@ -595,7 +595,7 @@ int dvf_head_seg_dgrad(const dvf_conv_desc *d, const float *dpre, const float *w
     const int rc = head_fwd_launch(segc, in, wseg, nullptr, din, d->C_out, d->N, d->H_in, d->W_in, DVF_ACT_NONE, 1.f, 0.f, 9,
                                    d->C_in * 9, 1, mask, st);
     if (rc) return rc;
-    dvf_plan_note(DVF_K_HEAD_SEG_DGRAD, segc);
+    dvf_note_head(DVF_K_HEAD_SEG_DGRAD, segc);
     return DVF_OK;
 }
 
@@ -605,7 +605,7 @@ int dvf_head_dgrad(const dvf_conv_desc *d, const float *dpre, const float *w, fl
     HEAD_DISPATCH(d->C_out, (head_dgrad_kernel<MO><<<grid, 256, (size_t)d->C_in * ((MO * 9 + 3) & ~3) * 4, st>>>(
                                 dpre, w, din, d->C_in, d->H_in, d->W_in, tilesX, mask)));
     DVF_LAUNCH_CHECK();
-    dvf_plan_note(DVF_K_HEAD_DGRAD, d->C_out);
+    dvf_note_head(DVF_K_HEAD_DGRAD, d->C_out);
     return DVF_OK;
 }
 
@@ -661,6 +661,6 @@ int dvf_head_wgrad(const dvf_conv_desc *d, const float *in, const float *dpre, f
         head_wgrad_finish_kernel<<<(n + 255) / 256, 256, 0, st>>>(part, dw, n, g.groups);
         DVF_LAUNCH_CHECK();
     }
-    dvf_plan_note(DVF_K_HEAD_WGRAD, d->C_out, part ? 1 : 0);
+    dvf_note_head(DVF_K_HEAD_WGRAD, d->C_out, part != nullptr);
     return DVF_OK;
 }

@@ -402,7 +402,7 @@ int plan_wgrad_reg(WgradArgs &a, WgradRegPlan &pl) {
 
 int launch_wgrad_reg(WgradArgs a, const WgradRegPlan &pl, hipStream_t st) {
     if (const char *e = dvf_tune("DVF_WG_DBG")) a.dbg = atoi(e);
-    dvf_plan_note(DVF_K_WGRAD, pl.MT, pl.NTW, pl.pf ? 1 : 0, a.CK, a.BH, a.PSPLIT, a.vp, a.S, 256, (int)pl.lds, a.KK);
+    dvf_note_wgrad_reg(pl.MT, pl.NTW, pl.pf, a.CK, a.BH, a.PSPLIT, a.vp, a.S, (int)pl.lds, a.KK);
     const int MT = pl.MT, NTW = pl.NTW;
     if (pl.pf) {
         if (MT == 2 && NTW == 2) conv_wgrad_kernel<2, 2, true><<<pl.grid, 256, pl.lds, st>>>(a);

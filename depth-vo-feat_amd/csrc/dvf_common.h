@@ -28,21 +28,50 @@ static inline const char *dvf_tune(const char *) { return nullptr; }
 
 // Plan log: every convolution entry point notes which kernel family and tiling it launched (thread-local, reset at the
 // entry); dvf_conv2d_last_plans() reads it back.  Tests use it to prove that the plans exercised by the parity cases
-// are the plans the benchmark step runs.
-enum { DVF_K_PIPE = 1, DVF_K_GATHER = 2, DVF_K_HEAD_FWD = 3, DVF_K_HEAD_DGRAD = 4, DVF_K_HEAD_WGRAD = 5, DVF_K_WGRAD = 6,
-       DVF_K_HEAD_SEG_DGRAD = 7, DVF_K_WGRAD_PIPE = 8, DVF_K_DCONVT_FWD = 9 };
-constexpr int DVF_PLAN_INTS = 12, DVF_PLAN_MAX = 8;
+// are the plans the benchmark step runs.  The record layout is the table above dvf_conv2d_last_plans in include/dvf_hip.h;
+// the dvf_note_* functions below are the only places that give a field its position.
 struct DvfPlanLog { int n; int rec[DVF_PLAN_MAX][DVF_PLAN_INTS]; };
 DvfPlanLog &dvf_plan_log();
 static inline void dvf_plan_reset() { dvf_plan_log().n = 0; }
 static inline void dvf_plan_note(int kernel, int a = 0, int b = 0, int c = 0, int d = 0, int e = 0, int f = 0, int g = 0,
-                                 int h = 0, int i = 0, int j = 0, int k = 0) {
+                                 int h = 0, int i = 0, int j = 0, int k = 0) {      // private to the note functions
     DvfPlanLog &l = dvf_plan_log();
     if (l.n >= DVF_PLAN_MAX) return;
     const int v[DVF_PLAN_INTS] = {kernel, a, b, c, d, e, f, g, h, i, j, k};
     for (int x = 0; x < DVF_PLAN_INTS; ++x) l.rec[l.n][x] = v[x];
     ++l.n;
 }
+
+constexpr int dvf_pipe_plan_flags(int out_mode, int ncls, int x4, int blocked, int lr, int npi) {
+    return out_mode | (ncls << DVF_PLAN_NCLS_SHIFT) | (x4 << DVF_PLAN_X4_SHIFT) | (blocked << DVF_PLAN_BLOCKED_SHIFT) |
+           (lr << DVF_PLAN_LR_SHIFT) | (npi << DVF_PLAN_NPI_SHIFT);
+}
+constexpr int dvf_wgrad_plan_tile(int MT, int TILE) { return MT | (TILE << DVF_PLAN_WG_TILE_SHIFT); }
+constexpr int dvf_wgrad_plan_lanes(int x4, int ordered) { return (x4 << DVF_PLAN_WG_X4_SHIFT) | (ordered << DVF_PLAN_WG_ORDERED_SHIFT); }
+static_assert(dvf_pipe_plan_flags(2, 4, 1, 1, 1, 12) == (2 | 4 << 4 | 1 << 8 | 1 << 9 | 1 << 10 | 12 << 11), "conv_pipe flags moved");
+static_assert(dvf_pipe_plan_flags(1, 4, 0, 0, 0, 0) == (1 | 4 << 4), "conv_gather flags moved");
+static_assert(dvf_wgrad_plan_tile(2, 32) == (2 | 32 << 8), "wgrad_pipe tile word moved");
+static_assert(dvf_wgrad_plan_lanes(1, 1) == (1 | 2) && dvf_wgrad_plan_lanes(0, 1) == 2, "wgrad_pipe lanes word moved");
+
+static inline void dvf_note_pipe(int MT, int NT, int WM, int CK, int TBU, int KS, int BN, int NST, int threads, int lds,
+                                 int out_mode, int ncls, int x4, bool blocked, int lr, int npi) {
+    dvf_plan_note(DVF_K_PIPE, MT, NT, WM, CK, TBU, KS, BN, NST, threads, lds, dvf_pipe_plan_flags(out_mode, ncls, x4, blocked, lr, npi));
+}
+static inline void dvf_note_gather(int MT, int NT, int CK, int KS, int lds, int out_mode, int ncls) {
+    dvf_plan_note(DVF_K_GATHER, MT, NT, 1, CK, 0, KS, 1, 1, 256, lds, dvf_pipe_plan_flags(out_mode, ncls, 0, 0, 0, 0));
+}
+static inline void dvf_note_wgrad_pipe(int MT, int TILE, int NTW, int x4, bool ordered, int CK, int stride, int pieces, int blocks,
+                                       int lds, int taps, int row_stride, int nseg) {
+    dvf_plan_note(DVF_K_WGRAD_PIPE, dvf_wgrad_plan_tile(MT, TILE), NTW, dvf_wgrad_plan_lanes(x4, ordered), CK, stride, pieces, blocks,
+                  lds, taps, row_stride, nseg);
+}
+static inline void dvf_note_wgrad_reg(int MT, int NTW, bool prefetch, int CK, int BH, int PSPLIT, int vec_p, int stride, int lds,
+                                      int taps) {
+    dvf_plan_note(DVF_K_WGRAD, MT, NTW, prefetch, CK, BH, PSPLIT, vec_p, stride, 256, lds, taps);
+}
+// the direct kernels of conv_head.hip: head_fwd (C_out, nseg), head_dgrad (C_out), head_wgrad (C_out, ordered),
+// head_seg_dgrad (segc), dconvt_fwd (C_out, KH)
+static inline void dvf_note_head(int kernel, int a, int b = 0) { dvf_plan_note(kernel, a, b); }
 
 // Sum over the 64 lanes of a wave; every lane ends with the total.
 __device__ __forceinline__ float wave_sum(float v) {

@@ -1,6 +1,7 @@
 """Convolution / transposed convolution with fused bias + activation as autograd Functions over the
 fp32-MFMA kernels of libdvf_hip.so, the small memory-bound ops around them, and the nn.Module shells whose
 parameter names and shapes equal the reference's (so ``state_dict`` files interchange)."""
+import contextlib
 import ctypes
 import math
 import weakref
@@ -199,7 +200,18 @@ def _wgrad_ws_floats(holder, desc, segc):
     return n
 
 
-GEOM_LOG = None   # set to a list(): ConvFn.forward appends the geometry of every call (tests: bench-shape parity)
+GEOM_LOG = None   # a list while a geom_log() is active: ConvFn.forward appends the geometry of every call (tests: bench-shape parity)
+
+
+@contextlib.contextmanager
+def geom_log(into=None):
+    """Switch GEOM_LOG on: the geometries go to the list `into`, or to a new one, which is yielded.  Restores on exit."""
+    global GEOM_LOG
+    saved, GEOM_LOG = GEOM_LOG, ([] if into is None else into)
+    try:
+        yield GEOM_LOG
+    finally:
+        GEOM_LOG = saved
 FUSE_RELU_BWD = True   # False: every layer runs its own activation backward pass (dvf_act_bwd), as in round 1
 
 

@@ -3,10 +3,14 @@
 The library is the product: there is no CPU or stock-torch fallback.  If the shared object is
 missing or a call returns an error code, this module raises.
 """
+import contextlib
 import ctypes
 import os
+import types
 
 import torch
+
+from .plans import *        # noqa: F401,F403  the plan record of dvf_conv2d_last_plans: KERNELS, K_*, PLAN_*, PlanRecord, ...
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (DVF_LIB: tools/ load the -DDVF_TUNING build, libdvf_hip_tuning.so, through this; the product path never sets it)
@@ -198,8 +202,6 @@ class KernelTimer:
     stream).  ``bench.py`` switches it on for one eager pass to measure per-kernel durations next to their
     algorithmic FLOPs / bytes; it is off (None) otherwise and costs nothing."""
 
-    FAMILY = {1: "pipe", 2: "gather", 3: "head", 4: "head", 5: "head", 6: "wgrad", 7: "head", 8: "wgrad_pipe", 9: "dconvt"}
-
     def __init__(self):
         self.records = []       # (kind, start_event, stop_event, flops, bytes, tag, kernel family)
         self._kernels = []      # per record: the kernel families the call launched, in launch order
@@ -218,12 +220,7 @@ class KernelTimer:
         ev.record(torch.cuda.current_stream())
         fam, kernels = "", ()
         if kind.startswith("conv_"):
-            # which kernels the call launched (dvf_conv2d_last_plans): the kernel family with the most work names the call
-            buf = (ctypes.c_int * 96)()
-            n = lib().dvf_conv2d_last_plans(buf, 96)
-            fams = [self.FAMILY.get(buf[i], "other") for i in range(0, n, 12)]
-            fam = next((f for f in ("pipe", "wgrad_pipe", "gather", "wgrad", "dconvt", "head") if f in fams), "other")
-            kernels = tuple(fams)
+            kernels, fam = timer_families(r.kernel for r in last_plans()[0])
         self.records.append((kind, start_ev, ev, float(flops), float(nbytes), tag, fam))
         self._kernels.append(kernels)
 
@@ -252,17 +249,41 @@ class KernelTimer:
         return out
 
 
-PLAN_LOG = None  # set to a set(): every convolution call adds (op, plan record) of the kernels it launched
+def last_plans(op=None):
+    """(records, full) of the convolution call just made on this thread: a PlanRecord per launch, and whether the log was
+    full, so that a further launch may have gone unrecorded.  The one reader of dvf_conv2d_last_plans."""
+    buf = (ctypes.c_int * (PLAN_INTS * PLAN_MAX))()
+    n = lib().dvf_conv2d_last_plans(buf, len(buf))
+    return records_of(buf, n, op), n == len(buf)
+
+
+PLAN_LOG = None  # a set() while a plan_log() is active: every convolution call adds the PlanRecords of the kernels it launched
+_PLAN_CAPTURE = None
+
+
+@contextlib.contextmanager
+def plan_log(into=None):
+    """Switch the plan log on (tests, tools): the records go to the set `into`, or to a new one.  Yields an object with
+    .records and .full_calls, the (op, number of records) of calls that filled the log; the innermost active one receives
+    them, and the state found on entry is restored on exit."""
+    global PLAN_LOG, _PLAN_CAPTURE
+    cap = types.SimpleNamespace(records=set() if into is None else into, full_calls=[])
+    saved = PLAN_LOG, _PLAN_CAPTURE
+    PLAN_LOG, _PLAN_CAPTURE = cap.records, cap
+    try:
+        yield cap
+    finally:
+        PLAN_LOG, _PLAN_CAPTURE = saved
 
 
 def note_plans(op):
-    """Read the plan records of the convolution call just made on this thread into PLAN_LOG (tests only)."""
+    """Read the plan records of the convolution call just made on this thread into PLAN_LOG."""
     if PLAN_LOG is None:
         return
-    buf = (ctypes.c_int * 96)()
-    n = lib().dvf_conv2d_last_plans(buf, 96)
-    for i in range(0, n, 12):
-        PLAN_LOG.add((op,) + tuple(buf[i:i + 12]))
+    recs, full = last_plans(op)
+    PLAN_LOG.update(recs)
+    if full and _PLAN_CAPTURE is not None:
+        _PLAN_CAPTURE.full_calls.append((op, len(recs)))
 
 
 TIMER = None    # set to a KernelTimer() to record

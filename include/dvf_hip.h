@@ -57,13 +57,38 @@ const char *dvf_error_string(int code);
 /* 1 when the library was built with -DDVF_TUNING (tuning knobs read from the environment, kernel ablation switches);
  * the product build returns 0: it reads no environment variable and cannot be switched into computing partial results. */
 int dvf_build_has_tuning(void);
-/* Which kernels the LAST dvf_conv2d_* call of this thread launched: records of 12 ints
- *   {kernel, MT, NT, WM, CK, TBU, KS, BN, NST, threads, lds_bytes, mode}   (kernel: 1 conv_pipe, 2 conv_gather,
- *   3 head_fwd {C_out, nseg}, 4 head_dgrad, 5 head_wgrad, 6 conv_wgrad {MT, NTW, prefetch, CK, BH, PSPLIT, vec_p, stride,
- *   threads, lds, KH*KW}, 7 head_seg_dgrad, 8 wgrad_pipe {MT | TILE << 8, NTW, x4 | ordered << 1, CK, stride, pieces,
- *   blocks, lds, KH*KW, row stride, nseg}, 9 dconvt_fwd {C_out, KH}) copied to the HOST array `out`; returns the number of
- *   ints written.
+/* Which kernels the LAST dvf_conv2d_* call of this thread launched: up to DVF_PLAN_MAX records (further ones are dropped) of
+ * DVF_PLAN_INTS ints, copied to the HOST array `out`; returns the number of ints written.  Int 0 of a record is its kernel
+ * family (DVF_K_*), the others are named per family, in order, unused ones 0 (the csrc/dvf_common.h note functions write
+ * them, dvf.lib.PlanRecord of the host binding reads them by these names):
+ *   conv_pipe       MT, NT, WM, CK, TBU, KS, BN, NST, threads, lds, flags
+ *                   flags = out_mode | ncls << 4 | x4 << 8 | blocked << 9 | lr << 10 | npi << 11   (DVF_PLAN_*_SHIFT / _MASK)
+ *                   out_mode 0 fused, 1 atomic, 2 ws; ncls parity classes; x4 16-byte lanes; blocked accumulation; lr the
+ *                   low-register form (two blocks a CU); npi its pieces per item
+ *   conv_gather     MT, NT, WM = 1, CK, TBU = 0, KS, BN = 1, NST = 1, threads, lds, flags = out_mode | ncls << 4
+ *   head_fwd        C_out, nseg
+ *   head_dgrad      C_out
+ *   head_wgrad      C_out, ordered   (1: per-block partials added in block order)
+ *   conv_wgrad      MT, NTW, prefetch, CK, BH, PSPLIT, vec_p, stride, threads, lds, taps = KH * KW
+ *   head_seg_dgrad  segc
+ *   wgrad_pipe      tile = MT | TILE << 8, NTW, lanes = x4 | ordered << 1, CK, stride, pieces, blocks, lds, taps, row_stride, nseg
+ *   dconvt_fwd      C_out, KH
  * The planner is shape dependent; tests use this to show that every plan of the benchmark step is parity-tested. */
+enum { DVF_K_PIPE = 1, DVF_K_GATHER = 2, DVF_K_HEAD_FWD = 3, DVF_K_HEAD_DGRAD = 4, DVF_K_HEAD_WGRAD = 5, DVF_K_WGRAD = 6,
+       DVF_K_HEAD_SEG_DGRAD = 7, DVF_K_WGRAD_PIPE = 8, DVF_K_DCONVT_FWD = 9 };
+#define DVF_PLAN_INTS 12
+#define DVF_PLAN_MAX 8
+#define DVF_PLAN_MODE_MASK 15 /* conv_pipe / conv_gather flags */
+#define DVF_PLAN_NCLS_SHIFT 4
+#define DVF_PLAN_NCLS_MASK 15
+#define DVF_PLAN_X4_SHIFT 8
+#define DVF_PLAN_BLOCKED_SHIFT 9
+#define DVF_PLAN_LR_SHIFT 10
+#define DVF_PLAN_NPI_SHIFT 11
+#define DVF_PLAN_WG_MT_MASK 255 /* wgrad_pipe tile */
+#define DVF_PLAN_WG_TILE_SHIFT 8
+#define DVF_PLAN_WG_X4_SHIFT 0 /* wgrad_pipe lanes */
+#define DVF_PLAN_WG_ORDERED_SHIFT 1
 int dvf_conv2d_last_plans(int *out, int max_ints);
 
 /* ---------------------------------------------------------------- inverse warp (image out)

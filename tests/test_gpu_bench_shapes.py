@@ -62,17 +62,14 @@ def test_fullsize_step_vs_oracle():
     dsd, psd, disp, pose = _step_nets()
     opt = FlatAdam(list(pose.parameters()) + list(disp.parameters()), lr=1e-3, weight_decay=1e-8)
     batch = synthetic_batch(B, H, W, seed=1234, device=DEV)
-    C.GEOM_LOG, L.PLAN_LOG = [], set()
-    try:
+    STATE["geoms"], STATE["step_plans"] = [], set()
+    with C.geom_log(STATE["geoms"]), L.plan_log(STATE["step_plans"]):
         loss, terms = unsupervise_losses(disp, pose, batch)
         opt.zero_grad()
         loss.backward()
         opt.join_wgrad()
         L.join_aux_streams()
         torch.cuda.synchronize()
-    finally:
-        STATE["geoms"], STATE["step_plans"] = C.GEOM_LOG, L.PLAN_LOG
-        C.GEOM_LOG, L.PLAN_LOG = None, None
     ref, grads, _ = osteps.step_unsupervise(dsd, psd, osteps.synthetic_batch(B, H, W, seed=1234), do_update=False)
     # fp64 run of the same oracle: ground truth for the noise floor of fp32 itself (ReLU gates and bilinear tap sets of
     # near-degenerate pixels flip under a different summation order; the deep 2x7 layers collect that noise)
@@ -214,14 +211,12 @@ def _check_deterministic(tag, form, run, ref_w, ref_b, failures):
     other.  Their plan records go to STATE['det_layer_plans']."""
     from dvf import conv as C
     from dvf import lib as L
-    saved = L.PLAN_LOG
-    L.PLAN_LOG = STATE.setdefault("det_layer_plans", set())
     C.set_deterministic(True)
     try:
-        (w1, b1), (w2, b2) = run(), run()
+        with L.plan_log(STATE.setdefault("det_layer_plans", set())):
+            (w1, b1), (w2, b2) = run(), run()
     finally:
         C.set_deterministic(False)
-        L.PLAN_LOG = saved
     errs = {f"det {form}wgrad": rel_err(w1, ref_w), f"det {form}bias": rel_err(b1, ref_b)}
     bad = {kk: v for kk, v in errs.items() if not v < TOL}
     if not torch.equal(w1, w2):
@@ -236,19 +231,14 @@ def _check_geometries(geoms, seed_base):
     """Run the geometries not parity-checked yet (any configuration); their plan records join STATE['layer_plans']."""
     from dvf import lib as L
     done = STATE.setdefault("checked_geoms", set())
-    plans = STATE.setdefault("layer_plans", set())
-    L.PLAN_LOG = set()
     failures = []
-    try:
+    with L.plan_log(STATE.setdefault("layer_plans", set())):
         for gi, geom in enumerate(geoms):
             if geom in done:
                 continue
             _check_geometry(seed_base + gi, geom, failures)
             done.add(geom)
             torch.cuda.empty_cache()
-    finally:
-        plans |= L.PLAN_LOG
-        L.PLAN_LOG = None
     assert not failures, failures
 
 
@@ -269,8 +259,9 @@ def test_bench_plans_are_the_tested_plans():
     assert step, "the library reported no plans"
     missing = sorted(step - layer)
     assert not missing, missing
-    kernels = {p[1] for p in step}
-    assert {1, 8} <= kernels, kernels                      # conv_pipe and wgrad_pipe at least
+    from dvf.lib import K_PIPE, K_WGRAD_PIPE
+    kernels = {p.kernel for p in step}
+    assert {K_PIPE, K_WGRAD_PIPE} <= kernels, kernels
     print("%d distinct plans in the step, all parity-tested; kernels used: %s" % (len(step), sorted(kernels)))
 
 
@@ -371,14 +362,11 @@ def test_other_bench_configs_geometries_and_plans(config):
     del mine, theirs
     sds = {n: {k: v.detach().cpu().clone() for k, v in net.state_dict().items()} for n, net in nets.items()}
     fwd_bwd()                                         # (first pass: packs, workspaces)
-    C.GEOM_LOG, L.PLAN_LOG = [], set()
-    try:
+    with C.geom_log() as geoms, L.plan_log() as log:
         total, terms = fwd_bwd()
         L.join_aux_streams()
         torch.cuda.synchronize()
-    finally:
-        geoms, step_plans = _distinct(C.GEOM_LOG), L.PLAN_LOG
-        C.GEOM_LOG, L.PLAN_LOG = None, None
+    geoms, step_plans = _distinct(geoms), log.records
     assert torch.isfinite(total).all(), float(total)
     assert float(opt.flat_g.abs().max()) > 0 and torch.isfinite(opt.flat_g).all()
     terms = {k: float(v) for k, v in terms.items()}
@@ -407,12 +395,6 @@ DET_TOL = 1e-5         # deterministic vs default arena, per parameter (rel_err)
 DET_TOL_FEAT = 1e-4    # FeatExtractor parameters: their gradients come through the photometric kernel's atomic scatter
 
 
-def _ordered_wgrad(rec):
-    """A weight-gradient plan record (as dvf.lib.note_plans stores it: op, kernel, fields) of an ordered path: wgrad_pipe
-    with its slabs in scratch (ws bit of field 3) or the direct head kernel with its partials buffer."""
-    return (rec[1] == 8 and rec[4] & 2) or (rec[1] == 5 and rec[3] == 1)
-
-
 @pytest.mark.parametrize("config", [2, 3, 4, 5])
 def test_deterministic_step_matches_default(config):
     import argparse
@@ -431,16 +413,14 @@ def test_deterministic_step_matches_default(config):
         return opt.flat_g.clone()
 
     # the first deterministic pass of the process grows the side streams' scratch (dvf/conv.py::_workspace)
-    C.GEOM_LOG, L.PLAN_LOG = [], set()
     C.set_deterministic(True)
     try:
-        det1 = arena()
-        geoms, det_plans = _distinct(C.GEOM_LOG), L.PLAN_LOG
-        C.GEOM_LOG, L.PLAN_LOG = None, None
+        with C.geom_log() as geoms, L.plan_log() as log:
+            det1 = arena()
+        geoms, det_plans = _distinct(geoms), log.records
         det2 = arena()
     finally:
         C.set_deterministic(False)
-        C.GEOM_LOG, L.PLAN_LOG = None, None
     default = arena()
     assert float(det1.abs().max()) > 0 and torch.isfinite(det1).all()
     worst, worst_feat = (0.0, ""), (0.0, "")
@@ -462,9 +442,10 @@ def test_deterministic_step_matches_default(config):
     del step, fwd_bwd, opt, nets, arena, det1, det2, default
     torch.cuda.empty_cache()
     # (c) every weight gradient of the deterministic step went through an ordered path
-    wrecs = [r for r in det_plans if r[0] == "wgrad"]
+    # (PlanRecord.ordered: wgrad_pipe with its slabs in scratch, the direct head kernel with its partials buffer)
+    wrecs = [r for r in det_plans if r.op == "wgrad"]
     assert wrecs, "the library reported no weight-gradient plans"
-    unordered = sorted(r for r in wrecs if not _ordered_wgrad(r))
+    unordered = sorted(r for r in wrecs if not r.ordered)
     assert not unordered, (config, unordered)
     # (d) and through plans the per-layer deterministic checks ran against torch CPU
     _check_geometries(geoms, 10000 * config)

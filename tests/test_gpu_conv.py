@@ -100,12 +100,9 @@ def test_conv_fwd_bwd(case):
         gx = [(torch.empty(x.numel() + 1, device=DEV)[1:].view(x.shape).copy_(x) if offset else x.clone().to(DEV))
               .requires_grad_(True) for x in xs]
         gw, gb = wt.clone().to(DEV).requires_grad_(True), b.clone().to(DEV).requires_grad_(True)
-        L.PLAN_LOG = set()
-        try:
+        with L.plan_log() as log:
             out = ConvFn.apply(gw, gb, (k, stride, pad, opad, transposed, act, alpha, beta, out_hw), *gx)
-        finally:
-            fwd_plans.append(sorted(r for r in L.PLAN_LOG if r[0] == "fwd"))
-            L.PLAN_LOG = None
+        fwd_plans.append(sorted(r for r in log.records if r.op == "fwd"))
         assert out.shape == ref.shape
         (out * gout.to(DEV)).sum().backward()
         assert rel_err(out, ref) < TOL, ("forward", offset)
@@ -115,8 +112,27 @@ def test_conv_fwd_bwd(case):
             assert rel_err(a.grad, r.grad) < TOL, (f"dgrad seg {i}", offset)
     if "offset" in name:
         aligned, unaligned = fwd_plans
-        assert [r[1] for r in aligned] == [1] and (aligned[0][12] >> 8) & 1, ("aligned: conv_pipe, 16-byte lanes", aligned)
-        assert unaligned and 1 not in [r[1] for r in unaligned], ("offset: unpacked kernels", unaligned)
+        assert [r.kernel for r in aligned] == [L.K_PIPE] and aligned[0].x4, ("aligned: conv_pipe, 16-byte lanes", aligned)
+        assert unaligned and L.K_PIPE not in [r.kernel for r in unaligned], ("offset: unpacked kernels", unaligned)
+
+
+def test_last_plans_reads_the_log_int_for_int():
+    """dvf.lib.last_plans against a raw read of dvf_conv2d_last_plans after one forward of c3x3_s1_relu's geometry."""
+    import ctypes
+    from dvf import lib as L
+    from dvf.conv import ConvFn
+    x = torch.randn(2, 16, 20, 36, device=DEV)
+    w, b = torch.randn(32, 16, 3, 3, device=DEV, requires_grad=True), torch.zeros(32, device=DEV, requires_grad=True)
+    ConvFn.apply(w, b, (3, 1, 1, 0, False, 1, 1.0, 0.0, None), x)
+    recs, full = L.last_plans("fwd")
+    buf = (ctypes.c_int * (L.PLAN_INTS * L.PLAN_MAX))()
+    n = L.lib().dvf_conv2d_last_plans(buf, len(buf))
+    raw = list(buf[:n])
+    assert n == L.PLAN_INTS and raw[0] == L.K_PIPE, raw
+    assert [v for r in recs for v in r[1:]] == raw and [r.op for r in recs] == ["fwd"], (recs, raw)
+    assert all(type(r) is L.PlanRecord and len(r) == 1 + L.PLAN_INTS for r in recs)
+    assert full is False
+    assert recs[0].kernel_name == "conv_pipe" and recs[0].MT == raw[1] and recs[0].lds == raw[10] and recs[0].x4 is True
 
 
 def test_conv_input_without_grad_skips_dgrad():

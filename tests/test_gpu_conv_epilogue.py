@@ -24,8 +24,6 @@ DEV = "cuda"
 HIT = set()
 NONE, RELU, SIG = X.ACT_NONE, X.ACT_RELU, X.ACT_SIGMOID_AFFINE
 ACT_NAME = {NONE: "none", RELU: "relu", SIG: "sigmoid"}
-MODE_NAME = {0: "fused", 1: "atomic", 2: "ws"}
-K_PIPE, K_GATHER, K_HEAD_FWD, K_HEAD_SEG_DGRAD = 1, 2, 3, 7            # DVF_K_* of csrc/dvf_common.h
 
 
 def geom(segs, cout, nhw, act=RELU, k=3, stride=1, pad=1, opad=0, transposed=False):
@@ -54,17 +52,18 @@ REQUIRED = (
 
 
 def cells_of(g, recs, masked):
-    """Cells hit by the plan records `recs` (op, kernel, 11 ints) of runs of geometry g; masked: the forms of its dgrad
+    """Cells hit by the plan records `recs` (dvf.lib.PlanRecord) of runs of geometry g; masked: the forms of its dgrad
     that ran ({"masked", "plain"} for check_geometry)."""
+    from dvf.lib import K_PIPE, K_GATHER, K_HEAD_FWD, K_HEAD_SEG_DGRAD
     segs, cout, cfg, (n, h, w), _ = g
     stride, transposed, act = cfg[1], cfg[4], cfg[5]
     acts = {ACT_NAME[act]} | ({"none"} if act == SIG else set())        # (a sigmoid layer also ran as its exact twin)
     out = set()
     for rec in recs:
-        op, kern = rec[0], rec[1]
+        op, kern = rec.op, rec.kernel
         if kern in (K_PIPE, K_GATHER) and op in ("fwd", "dgrad"):
             fam = "pipe" if kern == K_PIPE else "gather"
-            mt, ks, bn, mode, ncls = rec[2], rec[7], rec[8], MODE_NAME[rec[12] & 15], (rec[12] >> 4) & 15
+            mt, ks, bn, mode, ncls = rec.MT, rec.KS, rec.BN, rec.out_mode, rec.ncls
             out.add(("mode", fam, mode + (("_ge8" if ks >= 8 else "_lt8") if (fam == "pipe" and mode == "ws") else "")))
             m = cout if op == "fwd" else (segs[0] if len(segs) == 1 else None)      # (several segments: the record does not say whose)
             if m is not None:
@@ -83,7 +82,7 @@ def cells_of(g, recs, masked):
                 if not transposed and op == "dgrad":
                     out.add(("classes", "stride2"))
         if (kern, op) in ((K_HEAD_FWD, "fwd"), (K_HEAD_SEG_DGRAD, "dgrad")):
-            mo, c = (cout, sum(segs)) if kern == K_HEAD_FWD else (rec[2], cout)
+            mo, c = (cout, sum(segs)) if kern == K_HEAD_FWD else (rec.segc, cout)
             lowres = n * h * w <= 4 * 64 * 208 and mo <= 4 and c >= 32          # head_fwd_launch (csrc/conv_head.hip)
             out.add(("head_tile", "32x4" if lowres else "8x8"))
             if kern == K_HEAD_SEG_DGRAD:
@@ -152,11 +151,10 @@ def test_head_kernel_cells(name, g):
 
 
 # ---- C ABI route: ws = NULL (atomics), packed = NULL (gather kernel whatever the channel count)
-def _records(lib, op, into):
-    buf = (ctypes.c_int * TE.PLAN_BUF_INTS)()
-    n = lib.dvf_conv2d_last_plans(buf, TE.PLAN_BUF_INTS)
-    assert n < TE.PLAN_BUF_INTS, "the plan log is full: a further plan may have run unseen"
-    into |= {(op,) + tuple(buf[i:i + TE.PLAN_INTS]) for i in range(0, n, TE.PLAN_INTS)}
+def _records(L, op, into):
+    recs, full = L.last_plans(op)
+    assert not full, "the plan log is full: a further plan may have run unseen"
+    into |= set(recs)
 
 
 def run_abi(name, g, use_packed, use_ws):
@@ -185,7 +183,7 @@ def run_abi(name, g, use_packed, use_ws):
         pk, wsp, wsn = operands(0)
         L.check(lib.dvf_conv2d_fwd(geo.dref, inarr, geo.segarr, geo.nseg, pk, w.data_ptr(), b.data_ptr(), out.data_ptr(),
                                    wsp, wsn, L.stream_raw()), "dvf_conv2d_fwd")
-        _records(lib, "fwd", recs)
+        _records(L, "fwd", recs)
         dpre = ref.dpre.float().to(DEV)
         gins = [torch.full_like(x, float("nan")) for x in xs]
         ginarr = (ctypes.c_void_p * geo.nseg)(*[t.data_ptr() for t in gins])
@@ -193,7 +191,7 @@ def run_abi(name, g, use_packed, use_ws):
         pk, wsp, wsn = operands(1)
         L.check(lib.dvf_conv2d_dgrad(geo.dref, dpre.data_ptr(), pk, w.data_ptr(), ginarr, geo.segarr, geo.nseg, wsp, wsn,
                                      marr, L.stream_raw()), "dvf_conv2d_dgrad")
-        _records(lib, "dgrad", recs)
+        _records(L, "dgrad", recs)
         torch.cuda.synchronize()
         form = "masked" if masked else "plain"
         for what, got, want in [("fwd", out, ref.out)] + [(f"dx{i}", t, r) for i, (t, r) in enumerate(zip(gins, ref.dxs))]:

@@ -27,8 +27,6 @@ import test_gpu_conv_fuzz as TF
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 STATE = {"plans": set(), "done": set()}
-PLAN_INTS = 12
-PLAN_BUF_INTS = 96        # DVF_PLAN_MAX (8) records: dvf_conv2d_last_plans drops any further record silently
 
 EXTRA_CASES = [
     # name, geometry (segs, cout, cfg (k, stride, pad, opad, transposed, act, alpha, beta, out_hw), (N, H, W), need_in)
@@ -43,26 +41,12 @@ EXTRA_CASES = [
 
 @contextlib.contextmanager
 def plan_capture(into):
-    """PLAN_LOG on; every convolution call's records go to `into`.  A call that reports DVF_PLAN_MAX records may have run a
-    further plan that the log dropped: that fails the test."""
+    """dvf.lib.plan_log(into); a call that reports DVF_PLAN_MAX records may have run a further plan that the log dropped: that
+    fails the test."""
     from dvf import lib as L
-    calls = []
-    orig = L.note_plans
-
-    def note(op):
-        buf = (ctypes.c_int * PLAN_BUF_INTS)()
-        n = L.lib().dvf_conv2d_last_plans(buf, PLAN_BUF_INTS)
-        calls.append((op, n))
-        for i in range(0, n, PLAN_INTS):
-            into.add((op,) + tuple(buf[i:i + PLAN_INTS]))
-
-    saved, L.PLAN_LOG, L.note_plans = L.PLAN_LOG, set(), note
-    try:
-        yield calls
-    finally:
-        L.PLAN_LOG, L.note_plans = saved, orig
-    full = [c for c in calls if c[1] >= PLAN_BUF_INTS]
-    assert not full, ("a call filled the plan log (8 records): a ninth plan may have run unseen", full)
+    with L.plan_log(into) as cap:
+        yield cap
+    assert not cap.full_calls, ("a call filled the plan log (8 records): a ninth plan may have run unseen", cap.full_calls)
 
 
 def _to_dev(x, offset):
@@ -203,16 +187,12 @@ def _bench_step(config):
         for det in (False, True):
             C.set_deterministic(det)
             fwd_bwd()                                 # (first pass of a mode: packs, workspaces)
-            C.GEOM_LOG = []
-            with plan_capture(plans):
+            with C.geom_log(geoms), plan_capture(plans):
                 fwd_bwd()
                 L.join_aux_streams()
                 torch.cuda.synchronize()
-            geoms += C.GEOM_LOG
-            C.GEOM_LOG = None
     finally:
         C.set_deterministic(False)
-        C.GEOM_LOG = None
     del step, fwd_bwd, opt, nets
     torch.cuda.empty_cache()
     STATE[key] = (BS._distinct(geoms), plans)
@@ -336,22 +316,21 @@ def test_act_bwd_accumulates_exactly():
     assert not failures, failures
 
 
-# Kernel families (DVF_K_* of csrc/dvf_common.h) that no exact case reaches, with the reason.  Empty: every family ran.
+# Kernel families (dvf.lib.KERNELS) that no exact case reaches, with the reason.  Empty: every family ran.
 UNREACHED_FAMILIES = {}
-FAMILY_NAMES = {1: "conv_pipe", 2: "conv_gather", 3: "head_fwd", 4: "head_dgrad", 5: "head_wgrad", 6: "conv_wgrad",
-                7: "head_seg_dgrad", 8: "wgrad_pipe", 9: "dconvt_fwd"}
 
 
 def test_plan_family_coverage():
     """Runs after the cases above: every kernel family 1-9 appeared in an exact run (or is named in UNREACHED_FAMILIES)."""
     if not STATE["plans"]:
         pytest.fail("no exact case ran before this test (run the whole module)")
+    from dvf.lib import KERNELS
     seen = {}
     for rec in STATE["plans"]:
-        seen.setdefault(rec[1], set()).add(rec[0])
+        seen.setdefault(rec.kernel, set()).add(rec.op)
     print("exact plan coverage: %d records; " % len(STATE["plans"]) +
-          ", ".join("%d %s %s" % (f, FAMILY_NAMES[f], sorted(seen.get(f, ())) or "-") for f in sorted(FAMILY_NAMES)))
-    missing = sorted(set(FAMILY_NAMES) - set(seen) - set(UNREACHED_FAMILIES))
-    assert not missing, ("kernel families no exact case reached", [FAMILY_NAMES[f] for f in missing])
+          ", ".join("%d %s %s" % (f, KERNELS[f], sorted(seen.get(f, ())) or "-") for f in sorted(KERNELS)))
+    missing = sorted(set(KERNELS) - set(seen) - set(UNREACHED_FAMILIES))
+    assert not missing, ("kernel families no exact case reached", [KERNELS[f] for f in missing])
     stale = sorted(set(UNREACHED_FAMILIES) & set(seen))
     assert not stale, ("reached now: remove from UNREACHED_FAMILIES", stale)

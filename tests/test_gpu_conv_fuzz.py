@@ -107,17 +107,16 @@ def test_wgrad_envelope_deterministic(case):
     C.set_deterministic(True)
     try:
         for _ in range(2):
-            L.PLAN_LOG = set()
-            _, gw_grad, gb_grad = _hip_wgrad(case, xs, wt, b, gout)
-            runs.append((gw_grad, gb_grad, {r for r in L.PLAN_LOG if r[0] == "wgrad"}))
+            with L.plan_log() as log:
+                _, gw_grad, gb_grad = _hip_wgrad(case, xs, wt, b, gout)
+            runs.append((gw_grad, gb_grad, {r for r in log.records if r.op == "wgrad"}))
     finally:
         C.set_deterministic(False)
-        L.PLAN_LOG = None
     (w1, b1, plans), (w2, b2, _) = runs
     assert rel_err(w1, rw_grad) < TOL, (name, "det wgrad", rel_err(w1, rw_grad))
     assert rel_err(b1, rb_grad) < TOL, (name, "det bias", rel_err(b1, rb_grad))
     assert plans, name
-    unordered = sorted(r for r in plans if not ((r[1] == 8 and r[4] & 2) or (r[1] == 5 and r[3] == 1)))
+    unordered = sorted(r for r in plans if not r.ordered)
     if name in UNORDERED_IN_DETERMINISTIC_MODE:
         assert unordered, (name, "now runs an ordered path: remove it from UNORDERED_IN_DETERMINISTIC_MODE", sorted(plans))
         return

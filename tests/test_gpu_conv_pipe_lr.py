@@ -1,6 +1,6 @@
 """The low-register form of conv_pipe_kernel (csrc/conv_pipe.h: two blocks share a CU): forward and dgrad against torch CPU
 fp32 at the suite's 1e-4 (max-abs error / max-abs reference), and the routing of csrc/conv_pipe_host.h read back from the plan
-records (bit 10 of the last field: the form that ran; bits 11..: patch pieces per channel).
+records (dvf.lib.PlanRecord: lr, the form that ran; npi, patch pieces per channel).
 
 Two parts.
  * The product library.  It takes the form only on grids of more than one block per CU, so these cases are the smallest
@@ -92,18 +92,13 @@ def _run(case, operands):
         for x in gx:
             x._dvf_relu_tag = ReluTag()
     gw, gb = wt.clone().to(DEV).requires_grad_(True), b.clone().to(DEV).requires_grad_(True)
-    L.PLAN_LOG = set()
-    try:
+    with L.plan_log() as log:
         out = ConvFn.apply(gw, gb, (k, stride, pad, opad, transposed, 1, 1.0, 0.0, None), *gx)
         out.backward(gout.to(DEV))
         torch.cuda.synchronize()
-        recs = sorted(r for r in L.PLAN_LOG if r[1] == 1)          # DVF_K_PIPE
-    finally:
-        L.PLAN_LOG = None
     plans = {}
-    for r in recs:
-        plans.setdefault(r[0], []).append({"lr": (r[12] >> 10) & 1, "npi": r[12] >> 11, "x4": (r[12] >> 8) & 1, "ks": r[7],
-                                           "bn": r[8], "lds": r[11]})
+    for r in sorted(r for r in log.records if r.kernel == L.K_PIPE):
+        plans.setdefault(r.op, []).append({"lr": int(r.lr), "npi": r.npi, "x4": int(r.x4), "ks": r.KS, "bn": r.BN, "lds": r.lds})
     return out.detach(), [x.grad for x in gx], plans
 
 

@@ -14,7 +14,6 @@ from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-K_HEAD_WGRAD = 5          # DVF_K_HEAD_WGRAD of csrc/dvf_common.h
 TOL = 1e-4
 TOL_DET_VS_ATOMIC = 1e-5
 
@@ -34,12 +33,6 @@ def _reference(x, dy):
         for tb in range(3):
             dw[:, :, ta, tb] = torch.einsum("nmyx,ncyx->mc", dyd, xp[:, :, ta:ta + h, tb:tb + w])
     return dw
-
-
-def _last_plans(L):
-    buf = (ctypes.c_int * 96)()
-    n = L.lib().dvf_conv2d_last_plans(buf, 96)
-    return [tuple(buf[i:i + 12]) for i in range(0, n, 12)]
 
 
 @pytest.mark.parametrize("hw", SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
@@ -66,7 +59,7 @@ def test_head_wgrad_small(cout, hw):
                 dw = dw0.to(DEV) if acc else torch.full((cout, cin, 3, 3), 7.0, device=DEV)
                 L.check(lib.dvf_conv2d_wgrad(ctypes.byref(desc), inarr, segarr, 1, gdy.data_ptr(), dw.data_ptr(), acc, None, 0,
                                              ws.data_ptr() if ws_floats else None, ws_floats, L.stream_raw()), "dvf_conv2d_wgrad")
-                plans = _last_plans(L)
+                plans = [(r.kernel, r.C_out, r.ordered) for r in L.last_plans()[0][:1]]
                 torch.cuda.synchronize()
                 return dw.cpu(), plans
 
@@ -74,16 +67,16 @@ def test_head_wgrad_small(cout, hw):
                 tag = (cout, cin, n, h, w, acc)
                 want = ref + dw0.double() if acc else ref
                 atomic, plans = run(acc, 0)
-                assert plans and plans[0][:3] == (K_HEAD_WGRAD, cout, 0), (tag, plans)
+                assert plans and plans[0] == (L.K_HEAD_WGRAD, cout, 0), (tag, plans)
                 e = rel_err(atomic, want)
                 print(f"head_wgrad {tag}: atomic rel err {e:.2e}")
                 assert e <= TOL, (tag, e)
                 det1, plans = run(acc, need)
-                assert plans and plans[0][:3] == (K_HEAD_WGRAD, cout, 1), (tag, plans)
+                assert plans and plans[0] == (L.K_HEAD_WGRAD, cout, 1), (tag, plans)
                 det2, _ = run(acc, need)
                 assert torch.equal(det1, det2), (tag, float((det1 - det2).abs().max()))
                 assert rel_err(det1, want) <= TOL, (tag, rel_err(det1, want))
                 assert rel_err(det1, atomic) <= TOL_DET_VS_ATOMIC, (tag, rel_err(det1, atomic))
                 short, plans = run(acc, need - 1)          # a scratch one float too small: the atomic path, still correct
-                assert plans and plans[0][:3] == (K_HEAD_WGRAD, cout, 0), (tag, plans)
+                assert plans and plans[0] == (L.K_HEAD_WGRAD, cout, 0), (tag, plans)
                 assert rel_err(short, want) <= TOL, (tag, rel_err(short, want))

@@ -7,7 +7,6 @@ import torch
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-K_DCONVT_FWD = 9          # DVF_K_DCONVT_FWD of csrc/dvf_common.h: the thin transposed layers' direct kernel (upconv1, 32 -> 16)
 
 
 def _t4x4s2(geoms):
@@ -31,18 +30,14 @@ def test_unsupervise_skips_the_mask_decoder_bit_exactly(monkeypatch):
     batch = synthetic_batch(2, 64, 208, seed=1234, device=DEV)
 
     def fwd_bwd():
-        saved = C.GEOM_LOG, L.PLAN_LOG
-        C.GEOM_LOG, L.PLAN_LOG = [], set()
-        try:
+        with C.geom_log() as geoms, L.plan_log() as log:
             loss, terms = S.unsupervise_losses(disp, pose, batch)
             opt.zero_grad()
             loss.backward()
             opt.join_wgrad()
             L.join_aux_streams()
             torch.cuda.synchronize()
-            return {k: v.clone() for k, v in terms.items()}, opt.flat_g.clone(), C.GEOM_LOG, L.PLAN_LOG
-        finally:
-            C.GEOM_LOG, L.PLAN_LOG = saved
+        return {k: v.clone() for k, v in terms.items()}, opt.flat_g.clone(), geoms, log.records
 
     C.set_deterministic(True)
     try:
@@ -55,7 +50,8 @@ def test_unsupervise_skips_the_mask_decoder_bit_exactly(monkeypatch):
     assert len(_t4x4s2(geoms_full)) == 5, _t4x4s2(geoms_full)               # upconv5 .. upconv1 ran when asked to
     assert len(plans_full) > len(plans_skip) > 0, (len(plans_full), len(plans_skip))
     assert not _t4x4s2(geoms_skip), _t4x4s2(geoms_skip)
-    assert not any(p[1] == K_DCONVT_FWD and p[3] == 4 for p in plans_skip), sorted(plans_skip)
+    # (dconvt_fwd: the thin transposed layers' direct kernel -- upconv1, 32 -> 16)
+    assert not any(p.kernel == L.K_DCONVT_FWD and p.KH == 4 for p in plans_skip), sorted(plans_skip)
     assert len(geoms_full) - len(geoms_skip) == 9, (len(geoms_full), len(geoms_skip))   # five upconvs, four mask heads
     assert terms_skip.keys() == terms_full.keys()
     for k in terms_full:

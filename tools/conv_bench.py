@@ -56,21 +56,22 @@ def ab_forms(name, wt, b, cfg, xs, g):
     for _ in range(rounds):
         for m in forms:
             os.environ["DVF_PIPE_LR"] = m
-            L.TIMER, L.PLAN_LOG = L.KernelTimer(), set()
-            for _ in range(iters):
-                for x in xs:
-                    x.grad = None
-                out = ConvFn.apply(wt, b, cfg, *xs)
-                out.backward(g)
-            summ, plans = L.TIMER.summary(), L.PLAN_LOG
-            L.TIMER = L.PLAN_LOG = None
+            L.TIMER = L.KernelTimer()
+            with L.plan_log() as log:
+                for _ in range(iters):
+                    for x in xs:
+                        x.grad = None
+                    out = ConvFn.apply(wt, b, cfg, *xs)
+                    out.backward(g)
+            summ, plans = L.TIMER.summary(), log.records
+            L.TIMER = None
             for kind in t[m]:
                 t[m][kind].append(summ[kind]["ms"] / summ[kind]["calls"] * 1e3)
             res[m] = (out.detach().clone(), [x.grad.clone() for x in xs], plans)
     o0, g0, _ = res[forms[0]]
     eq = all(torch.equal(o0, res[m][0]) and all(torch.equal(a, c) for a, c in zip(g0, res[m][1])) for m in forms)
     for m in forms:
-        pipes = sorted((pl[0], pl[2:7], pl[10], pl[11], (pl[12] >> 10) & 1) for pl in res[m][2] if pl[1] == 1)
+        pipes = sorted((pl.op, (pl.MT, pl.NT, pl.WM, pl.CK, pl.TBU), pl.threads, pl.lds, int(pl.lr)) for pl in res[m][2] if pl.kernel == L.K_PIPE)
         line = f"{name:36s} LR={m}"
         for kind in ("conv_fwd", "conv_dgrad"):
             v = t[m][kind]

@@ -48,11 +48,10 @@ def account(tag):
     tot = med[0] + med[1] + med[3]
     clock = tot / (med[4] * 10.0)          # cycles per ns
     us = lambda c: c / clock / 1e3
-    pb = (ctypes.c_int * 96)()
-    npl = lib.dvf_conv2d_last_plans(pb, 96)
-    plans = " ".join("[k%d MT%d NT%d WM%d CK%d TBU%d KS%d BN%d NST%d thr%d lds%d m%x]" % tuple(pb[i:i + 12]) for i in range(0, npl, 12) if pb[i] == 1)
+    kern = L.K_WGRAD_PIPE if KIND == "wgrad" else L.K_PIPE
+    plans = " ".join("[%s %s]" % (r.kernel_name, " ".join("%s %s" % (f, getattr(r, f)) for f in L.PLAN_FIELDS[kern] + tuple(L.PLAN_PACKED[kern])))
+                     for r in L.last_plans()[0] if r.kernel == kern)
     if KIND == "wgrad":
-        plans = " ".join("[k%d MT|TILE %x NTW%d x4 %d CK%d S%d NPIq%d blocks%d lds%d T%d RSq%d nseg%d]" % tuple(pb[i:i + 12]) for i in range(0, npl, 12) if pb[i] == 8)
         tot = med[0] + med[1]
         clock = tot / (med[4] * 10.0)
         us = lambda c: c / clock / 1e3
