@@ -87,15 +87,16 @@ def _compare(tag, got, ref, failures):
             failures.append((tag, what, m))
 
 
-def check_geometry(name, geom, seed, offset=False):
+def check_geometry(name, geom, seed, offset=False, forms=(False, True)):
     """All four forms of one geometry against fp64, exactly.  A sigmoid-affine layer runs them with act = NONE; its sigmoid
-    run must take the same plans, and its forward is bounded per element (_check_sigmoid)."""
+    run must take the same plans, and its forward is bounded per element (_check_sigmoid).  forms: (False,) or (True,) runs
+    the plain or the fused pair alone, for a caller that spreads a large geometry's two fp64 references over two cases."""
     from dvf import conv as C
     failures = []
     sig = geom[2][5] == X.ACT_SIGMOID_AFFINE
     exact_geom = X.with_act(geom, X.ACT_NONE) if sig else geom
     ops = X.Operands(exact_geom, seed)
-    for fused in (False, True):
+    for fused in forms:
         ref = X.Reference(exact_geom, ops, relu_in=fused)
         for det in (False, True):
             for off in ((False, True) if offset and not fused else (False,)):
