@@ -98,6 +98,37 @@ def test_packed_weight_planner_is_host_only_and_consistent():
     assert lib.dvf_conv2d_packed_floats(ctypes.byref(up), L.int_array([256]), 1, 0) >= 256 * 128 * 9
 
 
+def test_product_library_ignores_the_tuning_environment():
+    """The convolution planners' tuning knobs (dvf_tune of csrc/dvf_common.h: NULL in the product build) are constants in the
+    product library: the five host-only size queries of a 3x3 64->128 layer at 4x32x104 answer the same with the variables
+    that move them in the tuning build (forced gather route, half-CU LDS budget, gather chunk cap, no wgrad_pipe) set."""
+    import ctypes
+    lib = L.lib()
+    assert not lib.dvf_build_has_tuning()
+    d = _desc(4, 64, 32, 104, 128)
+    segs = L.int_array([64])
+
+    def sizes():
+        return (lib.dvf_conv2d_packed_floats(ctypes.byref(d), segs, 1, 0), lib.dvf_conv2d_packed_floats(ctypes.byref(d), segs, 1, 1),
+                lib.dvf_conv2d_ws_floats(ctypes.byref(d), segs, 1, 0), lib.dvf_conv2d_ws_floats(ctypes.byref(d), segs, 1, 1),
+                lib.dvf_conv2d_wgrad_ws_floats(ctypes.byref(d), segs, 1))
+
+    before = sizes()
+    assert before[0] > 0 and before[1] > 0 and before[4] > 0, before
+    knobs = {"DVF_PIPE_PLAN": "0,0,0,0,-1", "DVF_PIPE_BIGLDS_KB": "76", "DVF_G_LDS_KB": "24", "DVF_WG_PIPE": "0"}
+    saved = {k: os.environ.get(k) for k in knobs}
+    os.environ.update(knobs)
+    try:
+        after = sizes()
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    assert after == before, (before, after)
+
+
 def test_bench_spawn_parent_makes_no_gpu_runtime_call():
     """`python bench.py --gpus N` without a launcher fork+execs its N ranks: the parent must not have loaded torch (whose
     device count goes through HIP/HSA) -- on the GPU pool an exec from a GPU-initialised process takes the machine down.
